@@ -10,13 +10,18 @@ Weights are freshly initialised (no checkpoints offline); the state lives in HBM
 protocol of the reference's notebooks/test_rodent.ipynb) and skips the Transition logging.
 
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full
     python bench.py --gpus 8 ...      # starts the 8 ranks itself (torch.distributed.run) before touching a GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  Besides the contract's keys the line carries
-`free_running`: the same measurement with the auto-reset wrapper off (with the reference's C.20 wrapper bug every
-env of the default workload is reset to its cached first state at every step after the tenth, so the default
-figure re-steps that first state; the free-running figure lets the envs evolve).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the `--steps` steps
+and prints the headline keys.  `--full` adds the legs that take runs of their own: `roofline` (step-kernel time from HIP
+events of an eager re-run), `free_running` (the same measurement with the auto-reset wrapper off: with the reference's
+C.20 wrapper bug every env of the default workload is reset to its cached first state at every step after the tenth,
+so the default figure re-steps that first state; the free-running figure lets the envs evolve), `cpu_baseline` (with
+the oracle compliance check) and `train_step`.  `--dump-outputs DIR` writes what the last timed step returned on rank 0
+(the env state and, with the policy, that step's Transition row) as DIR/<name>.npy; inputs are seeded, so two builds
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -43,13 +48,19 @@ F_ALG = 3.9e6 - 0.68e6  # step kernel only (the policy forward is a separate ker
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic_latest.json")
 HBM_PEAK_GBS = 8000.0
 VALU_PEAK_TFLOPS = 157.3
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: above this, the same seeded sample of envs is written from every array
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also measure roofline, free_running, cpu_baseline (+ compliance) "
+                    "and train_step; --no-free-running, --no-cpu-baseline, --no-parity, --no-train-step and "
+                    "--no-train-secondary leave parts of these out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step (rank 0) "
+                    "as DIR/<name>.npy, float32 (float64 where the path computes in float64)")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--clips", type=int, default=1, help="number of resident reference clips (synthesised from the "
                     "groom clip when > 1: SURVEY 8(d) config 4), random clip per env")
@@ -67,7 +78,10 @@ def parse_args():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle compliance check of the cpu_baseline leg")
     ap.add_argument("--config", choices=("rodent", "humanoid"), default="rodent", help="humanoid: BASELINE config 'Humanoid "
                     "imitation, num_envs=1024' (HumanoidTracking, synthetic standing clip, random actions; not the headline metric)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -227,6 +241,56 @@ def update_record(dev, iters: int = 60) -> dict:
             "note": "fp32 MFMA (v_mfma_f32_32x32x2_f32) peak = the fp32 vector peak on gfx950"}
 
 
+def step_outputs(state, data) -> dict:
+    """What the last timed step returned to its caller, on the host, env axis first: the env state and, on the policy
+    path, that step's Transition row (the last row of the unroll buffers, which the next unroll overwrites)."""
+    import numpy as np
+
+    ps = state.pipeline_state
+    t = {"state.obs": state.obs, "state.reward": state.reward, "state.done": state.done, "state.qpos": ps.qpos,
+         "state.qvel": ps.qvel}
+    if data is not None:
+        t.update({f"transition.{k}": getattr(data, k)[-1] for k in
+                  ("observation", "action", "reward", "discount", "next_observation")})
+        t.update({f"transition.{g}.{k}": v[-1] for g, d in data.extras.items() for k, v in d.items()})
+    out = {}
+    for k, v in t.items():
+        a = v.detach().cpu().numpy()
+        out[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    return out
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array; above DUMP_CAP_BYTES in all, the same fixed, seeded sample of env rows of each."""
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        n = next(iter(arrays.values())).shape[0]
+        idx = np.sort(np.random.default_rng(0).choice(n, int(n * DUMP_CAP_BYTES // total), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def traffic_record(B: int):
+    """(bytes per step-kernel launch, source) from TRAFFIC_FILE, or (None, None) when it is absent or was taken with other
+    kernel sources or another env count."""
+    if not os.path.exists(TRAFFIC_FILE):
+        return None, None
+    import hashlib
+
+    tf = json.load(open(TRAFFIC_FILE))
+    hsh = hashlib.sha256()
+    for f in ("vnl_body.h", "vnl_lib.hip", "vnl_types.h"):
+        hsh.update(open(os.path.join(ROOT, "vnl-brax-imitation_amd", "csrc", f), "rb").read())
+    # a figure taken with other kernel sources (or another env count) is stale: reported as null, never as measured
+    if int(tf.get("envs", 0)) == B and tf.get("kernel_sources_sha256") == hsh.hexdigest():
+        return float(tf["bytes_per_launch"]), tf.get("source")
+    return None, None
+
+
 def main() -> None:
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -296,13 +360,16 @@ def main() -> None:
         assert policy.__name__ == "policy_hip"
         gdev = torch.Generator(device=dev).manual_seed(99 + rank)
 
-    def measure(autoreset: bool, steps: int, warmup: int) -> dict:
-        """W untimed + K timed steps of the hot path, barrier + synchronize on both sides, MAX over ranks; the step
-        kernel's own duration from HIP events recorded around its launch on the launch stream."""
+    def measure(autoreset: bool, steps: int, warmup: int, kernel_time: bool, outputs: bool = False) -> dict:
+        """W untimed + K timed steps of the hot path, barrier + synchronize on both sides, MAX over ranks; with
+        `kernel_time`, the step kernel's own duration from HIP events recorded around its launch on the launch stream in
+        an eager re-run after the timed region;
+        with `outputs`, what the last timed step returned (step_outputs)."""
         env = AutoResetWrapper(EpisodeWrapper(base, episode_length=150, action_repeat=1)) if autoreset else base
         gen = torch.Generator(device="cpu")
         gen.manual_seed(1234 + rank)  # independent stream per rank: envs shard, nothing crosses the links
         state = env.reset(gen)
+        last = None  # the Transition buffers of the last unroll run (policy path)
         ev = []
         orig_step = base.step
         k_ev = [None]
@@ -332,38 +399,42 @@ def main() -> None:
             graphed = acting.GraphedUnroll(env, state, policy, gdev, unroll, extra_fields=extra) if (autoreset and not args.eager) else None
 
             def run(k0, n, timed, events=False):
-                nonlocal state
+                nonlocal state, last
                 k_ev[0] = 0 if events else None
                 base.step = step_hook if events else orig_step
                 done = 0
                 while done < n:
                     chunk = min(unroll, n - done)
                     if graphed is not None and chunk == unroll and not events:
-                        state, _ = graphed()
+                        state, last = graphed()
                     else:
-                        state, _ = acting.generate_unroll(env, state, policy, gdev, chunk, extra_fields=extra)
+                        state, last = acting.generate_unroll(env, state, policy, gdev, chunk, extra_fields=extra)
                     done += chunk
                 base.step = orig_step
 
         torch.cuda.synchronize(dev)
         run(0, warmup, False)
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+        if kernel_time:
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
         base.kernel_events = None
         torch.cuda.synchronize(dev)
         if distributed:
             dist.barrier()
             torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        run(warmup, steps, True, events=graphed is None)
+        run(warmup, steps, True)
         torch.cuda.synchronize(dev)
         if distributed:
             dist.barrier()
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
         base.kernel_events = None
-        if graphed is not None:
-            # HIP events recorded inside a captured graph cannot be timed: the step kernel's launch duration comes from an
-            # eager re-run of the same hot path on the same envs right after the timed region (`kernel_ms_source`)
+        # (copied before anything below runs the path again: the graph's state and Transition buffers are reused)
+        outs = step_outputs(state, last) if outputs else None
+        if kernel_time:
+            # the step kernel's launch duration comes from an eager re-run of the same hot path on the same envs right after
+            # the timed region (`kernel_ms_source`) on every path: HIP events recorded inside a captured graph cannot be
+            # timed, and events kept out of the timed region leave `value` the same with and without --full
             nk = min(steps, 40)
             ev = ev[:nk]
             if args.random_actions:
@@ -376,33 +447,20 @@ def main() -> None:
             t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+        kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if kernel_time else None
         return dict(dt=dt, kernel_ms=kernel_ms, finite=bool(torch.isfinite(state.obs).all().item()),
-                    done_frac=float(state.done.float().mean().item()), graphed=graphed is not None)
+                    done_frac=float(state.done.float().mean().item()), graphed=graphed is not None, outputs=outs)
 
-    main_m = measure(not args.no_autoreset, args.steps, args.warmup)
+    main_m = measure(not args.no_autoreset, args.steps, args.warmup, args.full, outputs=bool(args.dump_outputs) and rank == 0)
+    if main_m["outputs"] is not None:
+        write_outputs(args.dump_outputs, main_m["outputs"])
     free_m = None
-    if not args.no_free_running and not args.no_autoreset:
-        free_m = measure(False, args.steps, args.warmup)
+    if args.full and not args.no_free_running and not args.no_autoreset:
+        free_m = measure(False, args.steps, args.warmup, True)
 
     if rank == 0:
-        dt, kernel_ms = main_m["dt"], main_m["kernel_ms"]
+        dt = main_m["dt"]
         value = world * B * args.steps / dt
-        per_gpu_kernel_rate = B / (kernel_ms * 1e-3)
-        hbm_gbs = B_ALG * B / (kernel_ms * 1e-3) / 1e9
-        valu_tflops = per_gpu_kernel_rate * F_ALG / 1e12
-        traffic, traffic_src = None, None
-        tpath = next((p_ for p_ in (os.path.join(ROOT, "gpurun_out", "traffic_latest.json"), TRAFFIC_FILE) if os.path.exists(p_)), None)
-        if tpath:
-            import hashlib
-
-            tf = json.load(open(tpath))
-            hsh = hashlib.sha256()
-            for f in ("vnl_body.h", "vnl_lib.hip", "vnl_types.h"):
-                hsh.update(open(os.path.join(ROOT, "vnl-brax-imitation_amd", "csrc", f), "rb").read())
-            # a figure taken with other kernel sources (or another env count) is stale: reported as null, never as measured
-            if int(tf.get("envs", 0)) == B and tf.get("kernel_sources_sha256") == hsh.hexdigest():
-                traffic, traffic_src = float(tf["bytes_per_launch"]), tf.get("source")
         workload = ("humanoid imitation rollout (HumanoidTracking, synthetic standing clip), " if args.config == "humanoid" else
                     "rodent imitation rollout, ") + (
                     ("" if args.config == "humanoid" else "single groom clip, " if args.clips == 1 else
@@ -430,10 +488,19 @@ def main() -> None:
                      "(scale 0.9); start frames / reset noise from torch Philox"),
             "config": {"workload": workload, "envs_per_gpu": B, "clips": args.clips,
                        "parallelism": f"env-sharded x{world}, no data-path collective"},
+            "finite": main_m["finite"],
+            "done_frac_last_step": main_m["done_frac"],
+        }
+        if args.full:
+            kernel_ms = main_m["kernel_ms"]
+            per_gpu_kernel_rate = B / (kernel_ms * 1e-3)
+            hbm_gbs = B_ALG * B / (kernel_ms * 1e-3) / 1e9
+            valu_tflops = per_gpu_kernel_rate * F_ALG / 1e12
+            traffic, traffic_src = traffic_record(B)
             # The fused step kernel is bound by the FP32 vector ALU / dependent on-chip latency, not by HBM or MFMA
             # (~500 flop per HBM byte), so the roofline is priced against the fp32 VALU peak; the HBM
             # figures (what north_star asks to see) are kept beside it.
-            "roofline": {
+            out["roofline"] = {
                 "bound": "valu",
                 "kernel": "vnl_step_kernel",
                 "achieved": valu_tflops,
@@ -444,8 +511,8 @@ def main() -> None:
                 "traffic_source": traffic_src,
                 "kernel_ms": kernel_ms,
                 "kernel_ms_source": ("HIP events around the step-kernel launches of an eager re-run of the hot path right after "
-                                     "the timed region (events inside the replayed hipGraph cannot be timed)" if main_m["graphed"]
-                                     else "HIP events around the step-kernel launches of the timed region, on the launch stream"),
+                                     "the timed region, on the launch stream (events inside the replayed hipGraph cannot be "
+                                     "timed; outside the timed region they cannot slow it)"),
                 "algorithmic_flops_per_launch": F_ALG * B,
                 "algorithmic_flops_note": "SURVEY 8(d) tree-sparse ESTIMATE at worst-case iteration counts, not a count of executed "
                                           "flops: `achieved` and `frac` are upper bounds of the useful fp32 rate",
@@ -453,10 +520,7 @@ def main() -> None:
                 "hbm_achieved_gbs": hbm_gbs,
                 "hbm_peak_gbs": HBM_PEAK_GBS,
                 "hbm_frac": hbm_gbs / HBM_PEAK_GBS,
-            },
-            "finite": main_m["finite"],
-            "done_frac_last_step": main_m["done_frac"],
-        }
+            }
         if free_m is not None:
             out["free_running"] = {
                 "value": world * B * args.steps / free_m["dt"], "unit": "env-steps/s",
@@ -464,18 +528,18 @@ def main() -> None:
                 "finite": free_m["finite"], "done_frac_last_step": free_m["done_frac"],
                 "note": "same hot path with the auto-reset wrapper off: envs evolve freely for warmup + steps control steps",
             }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(base, num_envs=1024)
             if not args.no_parity and args.config == "rodent" and args.clips == 1:
                 try:
                     out["cpu_baseline"]["compliance"] = parity_compliance(RodentTracking, clip, H.env_kwargs(), dev)
                 except Exception as e:  # the checker must not take the measurement down
                     out["cpu_baseline"]["compliance"] = {"error": repr(e)}
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
     # ---- full training step ("report rollout-only and full-train-step numbers separately") -------------
     train_rec = None
-    do_train = (not args.no_train_step and args.config == "rodent" and not args.random_actions and args.clips == 1 and
+    do_train = (args.full and not args.no_train_step and args.config == "rodent" and not args.random_actions and args.clips == 1 and
                 (world == 1 or args.train_step_multi))
     if do_train:
         torch.cuda.empty_cache()
@@ -495,7 +559,8 @@ def main() -> None:
                 raise
             train_rec = {"error": repr(e)}
     if rank == 0:
-        out["train_step"] = train_rec
+        if args.full:
+            out["train_step"] = train_rec
         print(json.dumps(out), flush=True)
     if distributed:
         dist.destroy_process_group()

@@ -43,6 +43,22 @@ def reference_clip() -> pp.ReferenceClip:
     return pp.process_qpos(model(), golden_qpos())
 
 
+def model_digest(m: mjcf.CompiledModel) -> str:
+    """sha256 over a compiled model's names, scalars and arrays (dtype, shape, bytes), in key order."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for k in sorted(m.names):
+        h.update(f"n {k} {'|'.join(m.names[k])}\n".encode())
+    for k in sorted(m.scalars):
+        h.update(f"s {k} {float(m.scalars[k])!r}\n".encode())
+    for k in sorted(m.arrays):
+        a = np.ascontiguousarray(m.arrays[k])
+        h.update(f"a {k} {a.dtype.str} {a.shape}\n".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
 def env_kwargs() -> dict:
     kw = dict(configs.RODENT_ENV_ARGS)
     kw["model"] = model()

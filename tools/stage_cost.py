@@ -18,7 +18,7 @@ def run(stage, count):
     env = dict(os.environ, VNL_LIB=os.path.join(ROOT, "vnl-brax-imitation_amd", "csrc", "libvnl_knobs.so"))  # build.py --knobs
     if count:
         env["VNL_DBG_REPEAT"] = f"{stage}:{count}"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--no-autoreset", "--random-actions"], env=env, capture_output=True, text=True)
     if out.returncode != 0 or not out.stdout.strip():
         sys.exit("bench.py failed:\n" + out.stderr[-3000:])
