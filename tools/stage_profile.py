@@ -21,7 +21,8 @@ NAMES = ["kinematics", "body inertias (x2)", "bias: velocity prefix", "bias: acc
          "solve: warm-start choice (2 J*v + costs)", "solve: J'f + first M^-1 grad", "iter: convergence test + |search|",
          "iter: J*search", "iter: qg sums", "iter: line search", "iter: qacc / Ma / Jaref update", "iter: gauss terms",
          "iter: J'f + cost", "iter: gradient", "iter: M^-1 grad", "iter: beta + search update", "solve tail / loop exit",
-         "euler: M^-1 rhs", "euler: integrate", "step: tables + state load + rtrunk", "step: reward / obs / traj / store"]
+         "euler: M^-1 rhs", "euler: integrate", "step: tables + state load + rtrunk", "step: reward / obs / traj / store",
+         "newton: assemble H", "newton: factor H (its own stamps land in the factor: rows)", "newton: invert factor"]
 NAMES += ["-"] * (40 - len(NAMES))
 
 

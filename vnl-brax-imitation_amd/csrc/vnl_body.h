@@ -628,7 +628,10 @@ struct EnvWaveT {
     // reads were an L2 round trip in the middle of a serial chain
     VNL_FOR(i, MI(nv)) s[LO(LD) + madr(i)] += m.dof_armature[i] + diag_scale * m.dof_damping[i];
     VNL_SYNC();
-    if (MI(solver_newton) && diag_scale == vreal(0.)) {  // dense symmetric copy of qM: the Newton solver's Hessian and M * search
+    if (MI(solver_newton) == 2 && diag_scale == vreal(0.)) {  // qM in its own layout: the tree-sparse Newton route's Hessian and M * search
+      VNL_FOR(e, MI(nM)) s[LO(newt_M) + e] = s[LO(LD) + e];
+      VNL_SYNC();
+    } else if (MI(solver_newton) && diag_scale == vreal(0.)) {  // dense symmetric copy of qM: the Newton solver's Hessian and M * search
       const int nv = MI(nv);
       VNL_FOR(k, nv * nv) s[LO(newt_M) + k] = vreal(0.);
       VNL_SYNC();
@@ -647,20 +650,28 @@ struct EnvWaveT {
   // iteration k run in one parallel region; pair p -> (a, a+c) comes from one universal triangular
   // table (ordered by a+c, so a prefix of it enumerates any depth).  The division of row k by its
   // pivot is deferred to one final pass (row k is never touched again after iteration k).
-  VNL_HD void factor_lds() const {
+  VNL_HD void factor_lds() const { factor_lds(LO(LD), LO(dinv), false); }
+  // (LDb / dinvb: where the matrix sits and where its reciprocal pivots go -- LO(LD), or the Newton Hessian of the tree-sparse
+  // route; guard: a pivot that is not positive is replaced by VNL_MINVAL, as the dense Newton route's Cholesky does)
+  VNL_HD void factor_lds(int LDb, int dinvb, bool guard) const {
     // (A column-per-lane variant that keeps the pivot row in registers and broadcasts it with
     // v_readlane was measured 2x slower: one LDS round trip in flight per step.  What matters is the
     // number of independent LDS accesses in flight, so each lane streams one ancestor row, 8-wide.)
     for (int k = MI(nv) - 1; k >= 0; k--) {
       int adr_k = madr(k), dk = eadr(k) - adr_k;
-      vreal inv = vreal(1.) / s[LO(LD) + adr_k];
-      VNL_SERIAL { s[LO(dinv) + k] = inv; }
+      vreal piv = s[LDb + adr_k];
+      if (guard && !(piv > vreal(0.))) {
+        piv = VNL_MINVAL;
+        VNL_SERIAL { s[LDb + adr_k] = piv; }
+      }
+      vreal inv = vreal(1.) / piv;
+      VNL_SERIAL { s[dinvb + k] = inv; }
       if (dk == 0) continue;
       VNL_FOR(a1, dk) {  // one lane per ancestor row: row(anc_a)[0..len) -= tmp * row_k[a .. a+len)
         int a = a1 + 1, len = dk - a + 1;
-        vreal tmp = s[LO(LD) + adr_k + a] * inv;
-        const vreal* src = s + LO(LD) + adr_k + a;
-        vreal* dst = s + LO(LD) + madr(anc_of(adr_k + a));
+        vreal tmp = s[LDb + adr_k + a] * inv;
+        const vreal* src = s + LDb + adr_k + a;
+        vreal* dst = s + LDb + madr(anc_of(adr_k + a));
         int c = 0;
         for (; c + 8 <= len; c += 8) {  // all 16 loads of a trip are issued before the first store
           vreal x0 = src[c], x1 = src[c + 1], x2 = src[c + 2], x3 = src[c + 3];
@@ -682,8 +693,8 @@ struct EnvWaveT {
     VNL_SYNC();
     VNL_FOR(i, MI(nv)) {
       int adr = madr(i), dep = eadr(i) - adr;
-      vreal di = s[LO(dinv) + i];
-      for (int t = 1; t <= dep; t++) s[LO(LD) + adr + t] *= di;
+      vreal di = s[dinvb + i];
+      for (int t = 1; t <= dep; t++) s[LDb + adr + t] *= di;
     }
     VNL_SYNC();
   }
@@ -780,22 +791,29 @@ struct EnvWaveT {
   // shallow (rodent: depth <= 13), and registers for columns they do not have would be dead weight.
   template <int NSET, int MAXD, bool SOLVE = false, int MAXD1 = MAXD>
   VNL_HD void factor_rows(bool with_loop = true, int rhs = 0) const {
+    factor_rows_at<NSET, MAXD, SOLVE, MAXD1>(with_loop, rhs, LO(LD), LO(dinv), (LO(Ma) + 3) & ~3);
+  }
+  // (LDb / dinvb / scb: the matrix, its reciprocal pivots and the scratch lines -- qM's factor in LO(LD) with the lines in the
+  // dead CG vectors, or the tree-sparse Newton Hessian with the lines in the pool (newton_factor_tree); GUARD: a pivot that is
+  // not positive is replaced by VNL_MINVAL, as the dense Newton route's Cholesky does)
+  template <int NSET, int MAXD, bool SOLVE = false, int MAXD1 = MAXD, bool GUARD = false>
+  VNL_HD void factor_rows_at(bool with_loop, int rhs, int LDb, int dinvb, int scb) const {
     static_assert(MAXD % 12 == 0 || MAXD == 16, "columns are processed in chunks of 12 (or 16)");
     constexpr int CH = MAXD % 12 == 0 ? 12 : 16;
     auto qd = [](int q) constexpr { return (NSET == 2 && q == 1) ? MAXD1 : MAXD; };
     vreal rr[NSET][MAXD], dg[NSET];
     int dep[NSET], last[NSET];
-    const int sc = (LO(Ma) + 3) & ~3;  // Ma|grad|Mgrad|search are dead while factorising; VNL_FAC_LINES * (MAXD + 4) floats
+    const int sc = scb;  // (qM: Ma|grad|Mgrad|search are dead while factorising); VNL_FAC_LINES * (MAXD + 4) floats
 #pragma unroll
     for (int q = 0; q < NSET; q++) {
       int a = (int)lane + q * VNL_LANES;
       bool ok = a < MI(nv);
       int adr = ok ? madr(a) : 0, d = ok ? eadr(a) - adr : 0;
       dep[q] = d, last[q] = ok ? a + ndesc(a) : -1;
-      dg[q] = ok ? s[LO(LD) + adr] : vreal(1.);
+      dg[q] = ok ? s[LDb + adr] : vreal(1.);
 #pragma unroll
       for (int c = 0; c < MAXD; c++)
-        if (c < qd(q)) rr[q][c] = c < d ? s[LO(LD) + adr + d - c] : vreal(0.);
+        if (c < qd(q)) rr[q][c] = c < d ? s[LDb + adr + d - c] : vreal(0.);
     }
     // Schedule (host, build_dev_model): row j is the pivot of step dof_ftime[j], after all of its
     // descendants; rows with disjoint subtrees share a step, each with its own scratch line
@@ -829,6 +847,9 @@ struct EnvWaveT {
                 if (c < qd(q)) st4a(s + line + c, rr[q][c], rr[q][c + 1], rr[q][c + 2], rr[q][c + 3]);
             }
           }
+          if constexpr (GUARD) {
+            if (!(dg[q] > vreal(0.))) dg[q] = VNL_MINVAL;
+          }
           vreal inv = vnl_recip(dg[q]);
           s[line + MAXD] = inv;
           s[line + MAXD + 1] = vreal(a);  // exact: a < 2^24
@@ -836,7 +857,7 @@ struct EnvWaveT {
             s[line + MAXD + 2] = bb[q];
             myinv[q] = inv;
           } else {
-            s[LO(dinv) + a] = inv;
+            s[dinvb + a] = inv;
           }
         }
       }
@@ -935,11 +956,11 @@ struct EnvWaveT {
       int a = (int)lane + q * VNL_LANES;
       if (a < MI(nv)) {
         int adr = madr(a), d = dep[q];
-        vreal di = s[LO(dinv) + a];
-        s[LO(LD) + adr] = dg[q];
+        vreal di = s[dinvb + a];
+        s[LDb + adr] = dg[q];
 #pragma unroll
         for (int c = 0; c < MAXD; c++)
-          if (c < qd(q) && c < d) s[LO(LD) + adr + d - c] = rr[q][c] * di;
+          if (c < qd(q) && c < d) s[LDb + adr + d - c] = rr[q][c] * di;
       }
     }
     VNL_SYNC();
@@ -1949,8 +1970,11 @@ struct EnvWaveT {
   }
 
   // ---- Newton solver (solver.py _update_gradient, SolverType.NEWTON): Mgrad = H^-1 grad with the Hessian of the cost at the
-  // current active set, H = qM + J' diag(efc_D * active) J -- formed and Cholesky-factorised dense in LDS (small models: the
-  // reference selects it for the ant, nv 14, configs/env_config.yaml:16-21).  efc_J is materialised once per substep.
+  // current active set, H = qM + J' diag(efc_D * active) J.  Two routes (build_dev_model picks one, m.solver_newton):
+  //   1, dense: H formed and Cholesky-factorised dense in LDS, efc_J materialised once per substep (small models: the
+  //      reference selects Newton for the ant, nv 14, configs/env_config.yaml:16-21);
+  //   2, tree-sparse (newton_*_tree below): H has qM's sparsity, so it lives in the qLD layout and is factorised by the
+  //      same tree-sparse L'DL (any model, the rodent's 73 dofs / 303 rows among them).
   VNL_HD void newton_jacobian() const {
     const int nv = MI(nv);
     V3 n = v3(m.pnx, m.pny, m.pnz);
@@ -2030,6 +2054,100 @@ struct EnvWaveT {
     VNL_SYNC();
   }
 
+  // Tree-sparse route.  Every constraint row's Jacobian lives on ONE body's path to the root: a limit row on its dof, the four
+  // pyramid rows of a contact on the path of the body whose geom touches the plane (J(r, d) = cdof_d . w_r with the row's
+  // wrench w_r = [rel x p_r ; p_r], p_r = n +- mu t1 / n +- mu t2).  So J_r' D_r J_r is nonzero only where both dofs lie on
+  // that path, i.e. one is an ancestor of the other: H keeps qM's layout, entry (i, j) with j an ancestor of i (or i itself)
+  //     H(i, j) = qM(i, j) + u_i . cdof_j (+ D of dof i's active limit row on the diagonal),
+  //     u_i = sum over the active rows r of the contacts whose path holds dof i of D_r w_r (w_r . cdof_i),
+  // -- one lane per row of H, no J, no fill-in.  Active: D != 0 and Jaref < 0 (newton_solve, oracle slv_update_gradient).
+  VNL_HD void newton_hessian_tree() const {
+    const int Hb = LO(newt_H);
+    const V3 n = v3(m.pnx, m.pny, m.pnz);
+    const unsigned char* act = (const unsigned char*)(s + LO(act_list));
+    const int na = ((const int*)(s + LO(act_list)))[(MI(ncon) + 3) / 4];
+    VNL_FOR(i, MI(nv)) {
+      const S6 cd = ld6(LO(cdof) + 6 * i);
+      S6 u = S6{v3(0, 0, 0), v3(0, 0, 0)};
+      for (int j = 0; j < na; j++) {  // (the active contacts: typically a handful)
+        // (the contact is the same in every lane: its table entries come through scalar loads)
+        const int c = VNL_UNIFORM_I((int)act[j]), r0 = MI(nlimit) + 4 * c;
+        const int* seg = m.body_pathseg + 8 * VNL_UNIFORM_I(con_body(c));
+        bool on_path = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) on_path = on_path || (i >= (seg[k] & 0xff) && i < (seg[k] >> 8));
+        if (!on_path) continue;
+        const int g = m.con_geom[c] & 0xff;
+        const vreal D = s[LO(efc_D) + r0], mu = m.cg_mu[g];
+        const V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          if (!(s[LO(Jaref) + r0 + q] < vreal(0.))) continue;
+          const V3 p = n + (q < 2 ? t1 : t2) * ((q & 1) ? -mu : mu);
+          const S6 w = S6{cross(rel, p), p};
+          u = u + w * (D * dot(w, cd));
+        }
+      }
+      vreal lim = vreal(0.);
+      const int r = (m.dof_limrow[i] & 0x3ff) - 1;
+      if (r >= 0) {
+        const vreal D = s[LO(efc_D) + r];
+        if (D != vreal(0.) && s[LO(Jaref) + r] < vreal(0.)) lim = fabs(D);  // (J(r, i) = sign(D): its square is 1)
+      }
+      const int adr = madr(i), dep = eadr(i) - adr;
+      for (int t = 0; t <= dep; t++) {
+        const int e = adr + t;
+        s[Hb + e] = s[LO(newt_M) + e] + dot(u, ld6(LO(cdof) + 6 * anc_of(e))) + (t == 0 ? lim : vreal(0.));
+      }
+    }
+    VNL_SYNC();
+  }
+  // x <- H^-1 x: H assembled at the active set as Jaref stands, factorised in place (L'DL, pivots guarded), the factor inverted
+  // (build_dev_model admits this route only where the register-resident inversion applies) and applied like qM's
+  // (solve_inplace: tmp2 is its scratch; Ma .. search, the scratch of qM's own factorisation routines, are live here)
+  VNL_HD void newton_solve_tree(int x) const {
+    const int Hb = LO(newt_H), dinvb = LO(newt_H) + MI(nM);
+    newton_hessian_tree();
+    VNL_PROF(31);
+    newton_factor_tree(Hb, dinvb);
+    VNL_PROF(32);
+    invert_factor(Hb);
+    VNL_PROF(33);
+    solve_inplace(x, Hb, dinvb);
+  }
+  // L'DL of the Hessian in place: the register-resident row elimination of qM's factor() with its scratch lines in the part of
+  // the pool that the contact-wrench / dof prefix sums use (dead between constraint_force and the next jac_mul), else the LDS form
+  VNL_HD void newton_factor_tree(int Hb, int dinvb) const {
+    const int nv = MI(nv), md = MI(max_depth);
+    const int scb = (LO(P) + 3 * MI(nefc) + 3) & ~3, room = LO(smooth) - scb;
+    if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16 && VNL_FAC_LINES * (16 + 4) <= room)
+      factor_rows_at<VNL_ROWSETS_1, 16, false, 16, true>(true, 0, Hb, dinvb, scb);
+    else if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 36 && VNL_FAC_LINES * (36 + 4) <= room)
+      factor_rows_at<VNL_ROWSETS_1, 36, false, 36, true>(true, 0, Hb, dinvb, scb);
+    else if (nv <= VNL_ROWSETS_2 * VNL_LANES && md < 36 && VNL_FAC_LINES * (36 + 4) <= room && (MI(fac_nleaf) >> 8) < 16)
+      factor_rows_at<VNL_ROWSETS_2, 36, false, 16, true>(true, 0, Hb, dinvb, scb);
+    else factor_lds(Hb, dinvb, true);
+  }
+  // out = qM v with qM's tree-sparse entries (symmetric: row i's own entries, then column i in the rows of i's descendants)
+  VNL_HD void newton_mass_mul_tree(int v, int out) const {
+    const int Mb = LO(newt_M);
+    VNL_FOR(i, MI(nv)) {
+      const int adr = madr(i), dep = eadr(i) - adr, nd = ndesc(i);
+      vreal acc = s[Mb + adr] * s[v + i] + row_dot(adr, dep, v, Mb);
+      for (int k = i + 1; k <= i + nd; k++) acc += s[Mb + eadr(k) - dep] * s[v + k];  // entry (k, i): depth(k) - depth(i) into row k
+      s[out + i] = acc;
+    }
+    VNL_SYNC();
+  }
+  VNL_HD void newton_solve_any(int x) const {
+    if (MI(solver_newton) == 2) newton_solve_tree(x);
+    else newton_solve(x);
+  }
+  VNL_HD void newton_mass_mul_any(int v, int out) const {
+    if (MI(solver_newton) == 2) newton_mass_mul_tree(v, out);
+    else newton_mass_mul(v, out);
+  }
+
   // solver.solve (CG / Newton).  One env per wave: the while loops run with this env's own trip counts.
   VNL_HD void solve() const {
     const int nv = MI(nv), ne = MI(nefc);
@@ -2073,8 +2191,8 @@ struct EnvWaveT {
     VNL_SYNC();
     const bool newton = MI(solver_newton) != 0;
     if (newton) {
-      fresh().newton_jacobian();
-      fresh().newton_solve(LO(Mgrad));
+      if (MI(solver_newton) == 1) fresh().newton_jacobian();
+      fresh().newton_solve_any(LO(Mgrad));
     } else {
       fresh().solve_inplace(LO(Mgrad));
     }
@@ -2086,7 +2204,7 @@ struct EnvWaveT {
     }
     ss = vnl_wave_sum(ss), gp = vnl_wave_sum(gp);
     VNL_SYNC();
-    if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
+    if (newton) fresh().newton_mass_mul_any(LO(search), LO(mv));
     VNL_PROF(15);
 
     for (int it = 0; it < MI(iterations); it++) {
@@ -2148,7 +2266,7 @@ struct EnvWaveT {
       d1 = vnl_wave_sum(d1), gg = vnl_wave_sum(gg);
       VNL_SYNC();
       VNL_PROF(23);
-      if (newton) fresh().newton_solve(LO(tmp));
+      if (newton) fresh().newton_solve_any(LO(tmp));
       else fresh().solve_inplace(LO(tmp));
       VNL_PROF(24);
       vreal d2 = vdot(LO(grad), LO(tmp));
@@ -2166,7 +2284,7 @@ struct EnvWaveT {
       }
       ss = vnl_wave_sum(ss);
       VNL_SYNC();
-      if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
+      if (newton) fresh().newton_mass_mul_any(LO(search), LO(mv));
       VNL_PROF(25);
     }
   }
