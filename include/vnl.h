@@ -166,6 +166,23 @@ int vnl_env_step(vnl_env*, const float* action, const vnl_state* state, void* st
  * normalised root quaternion in state->qpos[e][3..7); nothing else of the state is touched. */
 int vnl_env_fk(vnl_env* env, const float* qpos, const vnl_state* state, void* stream);
 
+/* Domain randomisation (brax `randomization_fn`, MJX semantics): per-env values of four raw model fields, fixed until the
+ * next call (auto-reset leaves them as they are).  Device pointers, float64, row-major [num_envs][n]; a null field pointer
+ * means the model's value for every env:
+ *   cg_friction  [ncg]  sliding friction of each collidable geom's contact rows (column 0 of the compiled cg_friction)
+ *   act_gain     [nu]   gainprm[0]
+ *   dof_damping  [nv], dof_armature [nv]
+ * Derived constants (dof / body invweight0, meaninertia, scale) stay as compiled; the contact rows' mu and inverse weight are
+ * derived per env by the upload's float64 expression, so a domain equal to the compiled values gives bit-identical tables.
+ * Every value must be finite, friction > 0, damping and armature >= 0 (else VNL_ERR_ARG).  The call waits for `stream`,
+ * copies and derives into library-owned tables; reset / step then run the randomised kernels.  A null `vnl_domain*` clears
+ * the domain.  vnl_env_scratch reads the tables back: "dom_mu", "dom_invw" [num_envs][ncg], "dom_gain" [num_envs][nu],
+ * "dom_damp", "dom_arm" [num_envs][nv] (row stride = the returned count, vreal elements; no debug mode needed). */
+typedef struct vnl_domain {
+  const double *cg_friction, *act_gain, *dof_damping, *dof_armature;
+} vnl_domain;
+int vnl_env_set_domain(vnl_env* env, const vnl_domain* domain, void* stream);
+
 /* Bisection hooks.  The per-env working set lives in LDS; with debug on, every reset/step
  * also copies it to a device dump [num_envs][row_stride]: enable = 1 at the end of the kernel,
  * enable = 2 (step only) as the LAST forward pass of the step leaves it, i.e. before the Euler

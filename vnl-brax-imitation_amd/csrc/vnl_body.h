@@ -304,6 +304,27 @@ struct EnvWaveT {
   VNL_HD vreal* gqfrc_act() const { return st.qfrc_actuator + (size_t)e * MI(nv); }
   // library-owned global scratch of this env: the second inverse factor of a substep (invert_aba) and its reciprocal pivots (factor_aba), nM + nv elements
   VNL_HD vreal* fac2() const { return ev.fac2 + (size_t)e * (MI(nM) + MI(nv)); }
+  // The model parameters a domain may randomise (vnl_env_set_domain), every read of them goes through here: the shared DevModel
+  // table, or in a randomised instantiation (SP::dom, csrc/vnl_domain.hip) this env's row of the per-env table (global memory,
+  // read at the same points; 960 B per env for the rodent)
+  enum { P_MU, P_INVW, P_GAIN, P_DAMP, P_ARM };
+  template <int F>
+  VNL_HD vreal par(int i) const {
+    if constexpr (SP::dom) {
+      const VNL_CAS DevDomain& d = kc->dom;
+      if constexpr (F == P_MU) return d.cg_mu[(size_t)e * MI(ncg) + i];
+      else if constexpr (F == P_INVW) return d.cg_invweight[(size_t)e * MI(ncg) + i];
+      else if constexpr (F == P_GAIN) return d.act_gain[(size_t)e * MI(nu) + i];
+      else if constexpr (F == P_DAMP) return d.dof_damping[(size_t)e * MI(nv) + i];
+      else return d.dof_armature[(size_t)e * MI(nv) + i];
+    } else {
+      if constexpr (F == P_MU) return m.cg_mu[i];
+      else if constexpr (F == P_INVW) return m.cg_invweight[i];
+      else if constexpr (F == P_GAIN) return m.act_gain[i];
+      else if constexpr (F == P_DAMP) return m.dof_damping[i];
+      else return m.dof_armature[i];
+    }
+  }
   VNL_HD V3 gpos3(int b) const {
     const vreal* x = gxpos() + 3 * b;
     return V3{x[0], x[1], x[2]};
@@ -626,7 +647,7 @@ struct EnvWaveT {
     VNL_SYNC();
     // armature and (Euler step) h * damping on the diagonals, one lane per dof: inside the entry loop these two table
     // reads were an L2 round trip in the middle of a serial chain
-    VNL_FOR(i, MI(nv)) s[LO(LD) + madr(i)] += m.dof_armature[i] + diag_scale * m.dof_damping[i];
+    VNL_FOR(i, MI(nv)) s[LO(LD) + madr(i)] += par<P_ARM>(i) + diag_scale * par<P_DAMP>(i);
     VNL_SYNC();
     if (MI(solver_newton) == 2 && diag_scale == vreal(0.)) {  // qM in its own layout: the tree-sparse Newton route's Hessian and M * search
       VNL_FOR(e, MI(nM)) s[LO(newt_M) + e] = s[LO(LD) + e];
@@ -1040,8 +1061,8 @@ struct EnvWaveT {
       S[q][0] = c.a.x, S[q][1] = c.a.y, S[q][2] = c.a.z, S[q][3] = c.l.x, S[q][4] = c.l.y, S[q][5] = c.l.z;
       U[q][0] = v2r{f.a.x, f.a.x}, U[q][1] = v2r{f.a.y, f.a.y}, U[q][2] = v2r{f.a.z, f.a.z};
       U[q][3] = v2r{f.l.x, f.l.x}, U[q][4] = v2r{f.l.y, f.l.y}, U[q][5] = v2r{f.l.z, f.l.z};
-      const vreal arm = m.dof_armature[aa];
-      diag[q] = v2r{arm, arm + h * m.dof_damping[aa]};
+      const vreal arm = par<P_ARM>(aa);
+      diag[q] = v2r{arm, arm + h * par<P_DAMP>(aa)};
       adrs[q] = madr(aa), dep[q] = eadr(aa) - adrs[q];
       myline[q] = m.dof_fslot[aa] & 0xff;
       ftime[q] = ok ? m.dof_ftime[aa] : -1;
@@ -1502,7 +1523,7 @@ struct EnvWaveT {
     tree_accumulate(ca, 6);
     // qfrc_smooth starts as passive damping minus the bias force (springs / actuation added by smooth_forces)
     VNL_FOR(d, MI(nv))
-      s[LO(smooth) + d] = -m.dof_damping[d] * s[LO(qvel) + d] - dot(ld6(LO(cdof) + 6 * d), ld6(ca + 6 * m.dof_body[d]));
+      s[LO(smooth) + d] = -par<P_DAMP>(d) * s[LO(qvel) + d] - dot(ld6(LO(cdof) + 6 * d), ld6(ca + 6 * m.dof_body[d]));
     VNL_SYNC();
     VNL_PROF(4);
     return cv;
@@ -1529,7 +1550,7 @@ struct EnvWaveT {
         a = s[LO(act) + i];
         s[LO(actdot) + i] = (ctrl - a) / fmax(tau, VNL_MINVAL);
       }
-      s[frc + i] = m.act_gear[i] * m.act_gain[i] * a;
+      s[frc + i] = m.act_gear[i] * par<P_GAIN>(i) * a;
       if (!listed) s[adof + i] = vreal(m.act_dof[i]);  // exact: dof < 2^24
     }
     VNL_SYNC();
@@ -1638,7 +1659,7 @@ struct EnvWaveT {
         cpos0 = pos - n * (dist0 * vreal(0.5));
       }
       V3 t2 = cross(n, t1);
-      vreal mu = m.cg_mu[g], margin = m.cg_margin[g], invw = m.cg_invweight[g];
+      vreal mu = par<P_MU>(g), margin = m.cg_margin[g], invw = par<P_INVW>(g);
       S6 vel = ld6(cvel + 6 * bd);
       for (int q = 0; q < nc; q++) {
         int c = c0 + q, r0 = MI(nlimit) + 4 * c;
@@ -1746,7 +1767,7 @@ struct EnvWaveT {
       int c = act[j], g = m.con_geom[c] & 0xff, r0 = MI(nlimit) + 4 * c;
       const int* seg = m.body_pathseg + 8 * con_body(c);
       S6 vel = path_sum(Q, seg);
-      vreal mu = m.cg_mu[g];
+      vreal mu = par<P_MU>(g);
       V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
       V3 pv = vel.l + cross(vel.a, rel);
       vreal jn = dot(n, pv), j1 = dot(t1, pv) * mu, j2 = dot(t2, pv) * mu;
@@ -1796,7 +1817,7 @@ struct EnvWaveT {
           vreal D = s[LO(efc_D) + r0];
           if (D != vreal(0.)) {
             int g = m.con_geom[c] & 0xff;
-            vreal mu = m.cg_mu[g], f[4];
+            vreal mu = par<P_MU>(g), f[4];
             for (int q = 0; q < 4; q++) {
               vreal x = s[LO(Jaref) + r0 + q];
               f[q] = x < vreal(0.) ? -D * x : vreal(0.);
@@ -1992,7 +2013,7 @@ struct EnvWaveT {
       const S6 cd = ld6(LO(cdof) + 6 * d);
       const V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
       const V3 pv = cd.l + cross(cd.a, rel);
-      const vreal mu = m.cg_mu[g], jn = dot(n, pv), j1 = dot(t1, pv) * mu, j2 = dot(t2, pv) * mu;
+      const vreal mu = par<P_MU>(g), jn = dot(n, pv), j1 = dot(t1, pv) * mu, j2 = dot(t2, pv) * mu;
       s[LO(newt_J) + r0 * nv + d] = jn + j1, s[LO(newt_J) + (r0 + 1) * nv + d] = jn - j1;
       s[LO(newt_J) + (r0 + 2) * nv + d] = jn + j2, s[LO(newt_J) + (r0 + 3) * nv + d] = jn - j2;
     }
@@ -2078,7 +2099,7 @@ struct EnvWaveT {
         for (int k = 0; k < 4; k++) on_path = on_path || (i >= (seg[k] & 0xff) && i < (seg[k] >> 8));
         if (!on_path) continue;
         const int g = m.con_geom[c] & 0xff;
-        const vreal D = s[LO(efc_D) + r0], mu = m.cg_mu[g];
+        const vreal D = s[LO(efc_D) + r0], mu = par<P_MU>(g);
         const V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
 #pragma unroll
         for (int q = 0; q < 4; q++) {

@@ -7,6 +7,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <map>
 #include <string>
 #include <vector>
@@ -109,6 +111,12 @@ struct vnl_env {
   int spec = 0;           // 1: the kernels specialised for the rodent's dims and layout (VnlSpecRodent) run this env
   size_t lds_bytes = 0;
   int blocks_per_cu = 0;
+  // domain randomisation (vnl_env_set_domain): the model's values of the randomisable fields and what the contact rows'
+  // inverse weight is derived from, kept from the upload; the per-env tables [B][ncg | ncg | nu | nv | nv] once set
+  std::vector<double> mu0, gain0, damp0, arm0, cg_t;
+  double impratio = 1.0;
+  vreal* dom = nullptr;
+  int has_dom = 0;  // 1: vnl_env_reset / vnl_env_step launch the randomised instantiations (csrc/vnl_domain.hip)
   std::vector<void*> allocs;
   std::map<std::string, std::pair<int, int>> sections;  // name -> (offset, count)
 };
@@ -300,6 +308,9 @@ static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm)
   }
   return true;
 }
+
+// inverse weight of a contact's rows (constraint._instantiate_contact): at upload and, per env, in vnl_env_set_domain
+static double contact_invweight(double t, double mu, double impratio) { return (t + mu * mu * t) * 2 * mu * mu / impratio; }
 
 static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   DevModel& d = env->dm;
@@ -736,13 +747,17 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   {
     std::vector<double> mu(ng), iw(ng);
     double impratio = S("impratio");
+    env->cg_t.assign(ng, 0.0);
     for (int g = 0; g < ng; g++) {
       mu[g] = F("cg_friction")[3 * g];
       double t = F("body_invweight0")[0] + (hm->f.count("cg_body_invweight0") ? F("cg_body_invweight0")[g]
                                                                                 : F("body_invweight0")[2 * (size_t)I("cg_bodyid")[g]]);
-      iw[g] = (t + mu[g] * mu[g] * t) * 2 * mu[g] * mu[g] / impratio;  // constraint._instantiate_contact
+      iw[g] = contact_invweight(t, mu[g], impratio);
+      env->cg_t[g] = t;
     }
     UPF(cg_mu, mu) UPF(cg_invweight, iw)
+    env->impratio = impratio, env->mu0 = mu;
+    env->gain0 = F("act_gain"), env->damp0 = F("dof_damping"), env->arm0 = F("dof_armature");
   }
 #undef UPF
 #undef UPI
@@ -805,17 +820,7 @@ static void layout(vnl_env* env) {
 static bool same_layout(const WsLayout& a, const WsLayout& b) { return memcmp(&a, &b, sizeof(WsLayout)) == 0; }
 static bool same_dims(const VnlDims& a, const VnlDims& b) { return memcmp(&a, &b, sizeof(VnlDims)) == 0; }
 
-// (VNL_KERNEL_ATTR: empty in the product; csrc/build.py --spill sets a VGPR cap to force register spills to scratch,
-// the regression build for the "results must not depend on spilling" test.  VNL_SPEC_ATTR: the specialised instantiations
-// are held to the two waves per SIMD of the generic kernel -- with every bound a constant the compiler unrolls further and
-// would take a 257th register, i.e. half the occupancy)
-#ifndef VNL_KERNEL_ATTR
-#define VNL_KERNEL_ATTR
-#endif
-#define VNL_ENV_KERNEL __launch_bounds__(64) VNL_KERNEL_ATTR
-template <class SP>
-__global__ void VNL_ENV_KERNEL vnl_step_kernel(const KernelConsts* kc, DevState st, const vreal* action, vreal* dump, vreal* dump_mid,
-                                               int* trace);
+#include "vnl_env_kernels.h"
 
 extern "C" void vnl_env_destroy(vnl_env* env) {
   if (!env) return;
@@ -949,6 +954,21 @@ extern "C" int vnl_env_dims(const vnl_env* env, vnl_dims* o) {
 
 extern "C" int vnl_env_scratch(const vnl_env* env, const char* name, float** dev_ptr, int32_t* count) {
   if (!env || !name || !dev_ptr || !count) return fail(VNL_ERR_ARG, "vnl_env_scratch: null argument");
+  if (strncmp(name, "dom_", 4) == 0) {  // per-env parameter tables of a randomised env, [num_envs][count] (no debug needed)
+    if (!env->has_dom) return fail(VNL_ERR_ARG, "vnl_env_scratch: %s: the env has no domain (vnl_env_set_domain)", name);
+    const DevModel& d = env->dm;
+    const size_t B = (size_t)env->B;
+    const struct { const char* k; size_t off; int n; } tabs[] = {
+        {"dom_mu", 0, d.ncg}, {"dom_invw", B * d.ncg, d.ncg}, {"dom_gain", 2 * B * d.ncg, d.nu},
+        {"dom_damp", B * (2 * d.ncg + d.nu), d.nv}, {"dom_arm", B * (2 * d.ncg + d.nu + d.nv), d.nv}};
+    for (const auto& t : tabs)
+      if (strcmp(name, t.k) == 0) {
+        *dev_ptr = (float*)(env->dom + t.off);
+        *count = t.n;
+        return VNL_OK;
+      }
+    return fail(VNL_ERR_ARG, "unknown scratch section %s", name);
+  }
   if (!env->dump) return fail(VNL_ERR_ARG, "scratch dump is off: call vnl_env_debug(env, 1) before reset/step");
   if (strcmp(name, "solver_trace") == 0) {  // int32 [num_envs][n_frames][VNL_TRACE_INTS], contiguous (not inside the image)
     *dev_ptr = (float*)env->trace;
@@ -982,34 +1002,19 @@ extern "C" int vnl_env_debug(vnl_env* env, int32_t enable, int32_t* row_stride) 
 }
 
 // ----------------------------------------------------------------------------- kernels
-// One env per 64-lane workgroup; the env's whole working set lives in dynamic LDS (~25 KB ->
-// 6 workgroups per CU, 1536 envs in flight on 256 CUs).
-template <class SP>
-__global__ void VNL_ENV_KERNEL vnl_step_kernel(const KernelConsts* kc, DevState st, const vreal* action,
-                                                      vreal* dump, vreal* dump_mid, int* trace) {
-  VNL_LDS_DECL(lds);
-  const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
-  EnvWaveT<SP> w{k->m, k->ev, st, k->L, lds, blockIdx.x, threadIdx.x, k, nullptr};
-  w.step(action, dump_mid, trace);
-  if (dump) w.dump(dump);
-}
-
-template <class SP>
-__global__ void VNL_ENV_KERNEL vnl_reset_kernel(const KernelConsts* kc, DevState st, const int* start_frame,
-                                                       const vreal* noise, vreal* dump, int* trace) {
-  VNL_LDS_DECL(lds);
-  const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
-  EnvWaveT<SP> w{k->m, k->ev, st, k->L, lds, blockIdx.x, threadIdx.x, k, nullptr};
-  w.reset(start_frame, noise, trace);
-  if (dump) w.dump(dump);
-}
-
+// (vnl_step_kernel / vnl_reset_kernel: vnl_env_kernels.h)
 __global__ void __launch_bounds__(64) vnl_fk_kernel(const KernelConsts* kc, DevState st, const vreal* qpos) {
   VNL_LDS_DECL(lds);
   const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
   EnvWave w{k->m, k->ev, st, k->L, lds, blockIdx.x, threadIdx.x, k, nullptr};
   w.fk(qpos);
 }
+
+// launchers of the randomised instantiations (csrc/vnl_domain.hip: a translation unit of their own); return a hipError_t
+int vnl_domain_reset_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const int* start_frame,
+                      const vreal* noise, vreal* dump, int* trace);
+int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const vreal* action,
+                     vreal* dump, vreal* dump_mid, int* trace);
 
 static int to_dev_state(const vnl_state* s, DevState* d) {
   const void* ptrs[] = {s->qpos, s->qvel, s->act, s->qacc_warmstart, s->xpos, s->xquat, s->subtree_com1,
@@ -1035,6 +1040,11 @@ extern "C" int vnl_env_reset(vnl_env* env, const int32_t* start_frame, const flo
   if (rc != VNL_OK) return rc;
   DeviceGuard guard(env->device);  // the launch goes to the env's GPU whatever the caller's current device is
   if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+  if (env->has_dom) {
+    HIPCHK((hipError_t)vnl_domain_reset_(env->kc, env->spec, env->B, env->lds_bytes, stream, ds, (const int*)start_frame,
+                                         (const vreal*)noise, env->debug ? env->dump : nullptr, env->debug ? env->trace : nullptr));
+    return VNL_OK;
+  }
   if (env->spec)
     hipLaunchKernelGGL((vnl_reset_kernel<VnlSpecRodent>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
                        (const KernelConsts*)env->kc, ds, (const int*)start_frame, (const vreal*)noise,
@@ -1067,6 +1077,12 @@ extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* 
   if (rc != VNL_OK) return rc;
   DeviceGuard guard(env->device);
   if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+  if (env->has_dom) {
+    HIPCHK((hipError_t)vnl_domain_step_(env->kc, env->spec, env->B, env->lds_bytes, stream, ds, (const vreal*)action,
+                                        env->debug == 1 ? env->dump : nullptr, env->debug == 2 ? env->dump : nullptr,
+                                        env->debug ? env->trace : nullptr));
+    return VNL_OK;
+  }
   if (env->spec)
     hipLaunchKernelGGL((vnl_step_kernel<VnlSpecRodent>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
                        (const KernelConsts*)env->kc, ds, (const vreal*)action, env->debug == 1 ? env->dump : nullptr,
@@ -1076,6 +1092,78 @@ extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* 
                        (const KernelConsts*)env->kc, ds, (const vreal*)action, env->debug == 1 ? env->dump : nullptr,
                        env->debug == 2 ? env->dump : nullptr, env->debug ? env->trace : nullptr);
   HIPCHK(hipGetLastError());
+  return VNL_OK;
+}
+
+// Domain randomisation: per-env friction, actuator gain, damping and armature (brax / MJX semantics: the raw fields are
+// replaced, the derived constants -- dof / body invweight0, meaninertia, scale -- stay as compiled), except the contact rows'
+// mu and inverse weight, which the upload derives from friction and which are derived here per env by the same float64
+// expression: a domain equal to the compiled values gives bit-identical tables.  Synchronous: waits for `stream`, reads the
+// inputs to the host, validates, derives, writes the library-owned tables.
+extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* stream) {
+  if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_domain: null env");
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+#ifndef VNL_FORKJOIN_DEFINED
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (the inputs may have been written, the tables read, on the stream)
+#else
+  (void)stream;
+#endif
+  if (!dom) {
+    env->has_dom = 0;
+    return VNL_OK;
+  }
+  const DevModel& d = env->dm;
+  const size_t B = (size_t)env->B;
+  struct Field {
+    const char* name;
+    const double* src;
+    const std::vector<double>& model;
+    int n;
+    int rule;  // 0: > 0, 1: >= 0, 2: finite only
+  } fields[] = {{"cg_friction", dom->cg_friction, env->mu0, d.ncg, 0}, {"act_gain", dom->act_gain, env->gain0, d.nu, 2},
+                {"dof_damping", dom->dof_damping, env->damp0, d.nv, 1}, {"dof_armature", dom->dof_armature, env->arm0, d.nv, 1}};
+  std::vector<double> v[4];
+  for (int f = 0; f < 4; f++) {
+    const Field& F = fields[f];
+    v[f].resize(B * F.n);
+    if (F.src) {
+      if (F.n > 0) HIPCHK(hipMemcpy(v[f].data(), F.src, v[f].size() * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+      for (size_t e = 0; e < B; e++) std::copy(F.model.begin(), F.model.end(), v[f].begin() + e * F.n);
+    }
+    for (size_t k = 0; k < v[f].size(); k++) {
+      const double x = v[f][k];
+      const bool ok = std::isfinite(x) && (F.rule == 2 || (F.rule == 1 ? x >= 0 : x > 0));
+      if (!ok) {
+        char where[96];
+        snprintf(where, sizeof(where), "env %zu, index %zu (%g)", k / F.n, k % F.n, x);
+        return fail(VNL_ERR_ARG, F.rule == 0 ? "vnl_env_set_domain: %s must be finite and > 0: %s"
+                                 : F.rule == 1 ? "vnl_env_set_domain: %s must be finite and >= 0: %s"
+                                               : "vnl_env_set_domain: %s must be finite: %s",
+                    F.name, where);
+      }
+    }
+  }
+  // [B][ncg] mu | [B][ncg] invweight | [B][nu] gain | [B][nv] damping | [B][nv] armature, cast to vreal as the upload does
+  std::vector<vreal> tab;
+  tab.reserve(B * (2 * d.ncg + d.nu + 2 * d.nv));
+  for (double x : v[0]) tab.push_back((vreal)x);
+  for (size_t k = 0; k < v[0].size(); k++) tab.push_back((vreal)contact_invweight(env->cg_t[k % d.ncg], v[0][k], env->impratio));
+  for (int f = 1; f < 4; f++)
+    for (double x : v[f]) tab.push_back((vreal)x);
+  if (!env->dom) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, (tab.empty() ? 1 : tab.size()) * sizeof(vreal)));
+    env->allocs.push_back(p);
+    env->dom = (vreal*)p;
+  }
+  if (!tab.empty()) HIPCHK(hipMemcpy(env->dom, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
+  DevDomain dd;
+  dd.cg_mu = env->dom, dd.cg_invweight = env->dom + B * d.ncg, dd.act_gain = env->dom + 2 * B * d.ncg;
+  dd.dof_damping = dd.act_gain + B * d.nu, dd.dof_armature = dd.dof_damping + B * d.nv;
+  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, dom), &dd, sizeof(DevDomain), hipMemcpyHostToDevice));
+  env->has_dom = 1;
   return VNL_OK;
 }
 
@@ -1412,3 +1500,8 @@ extern "C" int vnl_adam_step(float* params, const float* grads, float* mu, float
 }
 
 // the policy-forward entry points (vnl_policy_*) live in vnl_policy.hip
+
+#ifdef VNL_FORKJOIN_DEFINED
+// host simulation (tests/hostsim): this file is its one translation unit, so the randomised instantiations come in here
+#include "vnl_domain.hip"
+#endif

@@ -195,16 +195,31 @@ constexpr WsLayout vnl_make_layout(const VnlDims& d) {
  * library selects such a kernel only for an env whose dims and layout EQUAL the constants (vnl_env_create checks). */
 struct VnlSpecGeneric {
   static constexpr bool fixed = false;
+  static constexpr bool dom = false; /* true: per-env parameter tables (VnlSpecDom) */
   static constexpr VnlDims D{};
   static constexpr WsLayout L{};
 };
 /* the reference's rodent (assets/rodent.xml as envs/rodent.py:39-63 compiles it), CG 6 / 6 */
 struct VnlSpecRodent {
   static constexpr bool fixed = true;
+  static constexpr bool dom = false;
   // (53 dynamic bodies: 13 of the model's 66 are welded to their parents and folded into them, vnl_lib.hip: fuse_welded_bodies)
   static constexpr VnlDims D{74, 73, 30, 53, 68, 32, 59, 67, 303, 1119, 6, 6, 1, 1, 35, 5, 36, 6 | (13 << 8), 0,
                              2 | (2 << 4) | (2 << 8) | (3 << 12), 2, 66};
   static constexpr WsLayout L = vnl_make_layout(D);
+};
+/* Domain randomisation (vnl_env_set_domain): the same kernel as BASE, with the five randomisable model tables read per env
+ * from KernelConsts::dom instead of the shared DevModel tables (EnvWaveT::par).  Instantiated in csrc/vnl_domain.hip only. */
+template <class BASE>
+struct VnlSpecDom : BASE {
+  static constexpr bool dom = true;
+};
+
+/* Per-env parameter tables of a randomised env, library-owned, row-major [env][i] (vnl_lib.hip: vnl_env_set_domain) */
+struct DevDomain {
+  const vreal *cg_mu, *cg_invweight; /* [B][ncg]: friction and the contact rows' inverse weight derived from it */
+  const vreal *act_gain;             /* [B][nu] */
+  const vreal *dof_damping, *dof_armature; /* [B][nv] */
 };
 
 /* Everything the env kernels read that does not change between launches, in one device buffer.  The kernels read
@@ -214,5 +229,6 @@ struct KernelConsts {
   DevModel m;
   DevEnv ev;
   WsLayout L;
+  DevDomain dom; /* (after L: the offsets of m, ev and L that the unrandomised kernels read stay as they are) */
 };
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 import torch
@@ -32,6 +32,10 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # tests/helpers.py `backend(...)`; None in any product use, where construction fails loudly without a HIP device.
 _TEST_BACKEND = None
 _METRICS = ("rcom", "rvel", "rtrunk", "rquat", "ract", "rapp", "termination_error")
+# the raw model fields a domain may set per env (include/vnl.h: vnl_domain) -> (vnl_dims field of n, smallest allowed value,
+# whether the bound itself is allowed; None: any finite value)
+DOMAIN_FIELDS = {"cg_friction": ("ngeom_collide", 0.0, False), "act_gain": ("nu", None, False),
+                 "dof_damping": ("nv", 0.0, True), "dof_armature": ("nv", 0.0, True)}
 
 
 def packaged_model_path(name: str = "rodent", scale_factor: Optional[float] = 0.9) -> str:
@@ -193,6 +197,68 @@ class RodentTracking(Env):
         new.__dict__.update(self._config_attrs)
         new._build(self._build_args[0], int(num_envs), *self._build_args[1:])
         return new
+
+    _domain = None  # {field: (num_envs, n) float64 tensor} of a randomised env (with_domain), else None
+
+    def with_domain(self, domain: Mapping[str, Any]) -> "RodentTracking":
+        """A NEW env of the same model, clip, parameters and num_envs whose envs each run with their own values of the raw
+        model fields in `domain` (brax `randomization_fn`, MJX semantics; include/vnl.h: vnl_env_set_domain):
+
+          cg_friction  (num_envs, ncg)  sliding friction of each collidable geom's contact rows
+          act_gain     (num_envs, nu)   actuator gain (gainprm[0])
+          dof_damping, dof_armature  (num_envs, nv)
+
+        A field left out keeps the model's value.  Derived constants (invweight0, meaninertia) stay as compiled; the contact
+        rows' inverse weight follows friction.  Values are fixed for the env's lifetime (auto-reset keeps them).  Neither this
+        env nor its CompiledModel is changed.  `with_num_envs` of the result carries NO domain: an eval env is randomised by a
+        call of its own.  Raises ValueError on an unknown field, a wrong shape or a bad value (non-finite, friction <= 0,
+        damping or armature < 0)."""
+        d = self.dims
+        tables = {}
+        for k, v in dict(domain).items():
+            if k not in DOMAIN_FIELDS:
+                raise ValueError(f"unknown domain field {k!r}: expected some of {sorted(DOMAIN_FIELDS)}")
+            dim, lo, closed = DOMAIN_FIELDS[k]
+            t = torch.as_tensor(v).detach().to(dtype=torch.float64)
+            shape = (self.num_envs, int(getattr(d, dim)))
+            if tuple(t.shape) != shape:
+                raise ValueError(f"domain field {k!r} must have shape {shape}, got {tuple(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"domain field {k!r} has non-finite values")
+            if lo is not None and not bool(((t >= lo) if closed else (t > lo)).all()):
+                raise ValueError(f"domain field {k!r} must be {'>=' if closed else '>'} {lo}")
+            tables[k] = t.to(self.device).contiguous()
+        new = object.__new__(type(self))
+        new.__dict__.update(self._config_attrs)
+        new._build(self._build_args[0], self.num_envs, *self._build_args[1:])
+        desc = _lib.Domain(**{k: C.c_void_p(t.data_ptr()) for k, t in tables.items()})
+        _lib.check(new._L, new._L.vnl_env_set_domain(new._env_h, C.byref(desc), new._stream()))  # (copies: synchronous)
+        new._domain = tables
+        return new
+
+    @property
+    def domain(self) -> Optional[Dict[str, torch.Tensor]]:
+        """The per-env field values this env was built with (with_domain), or None."""
+        return None if self._domain is None else dict(self._domain)
+
+    def domain_table(self, name: str) -> torch.Tensor:
+        """(num_envs, n) copy of one of the library's per-env tables of a randomised env (vnl_env_scratch "dom_mu",
+        "dom_invw", "dom_gain", "dom_damp", "dom_arm"): what the kernels read."""
+        ptr, cnt = C.c_void_p(), C.c_int32()
+        _lib.check(self._L, self._L.vnl_env_scratch(self._env_h, name.encode(), C.byref(ptr), C.byref(cnt)))
+        total = self.num_envs * cnt.value
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+            flat = torch.empty(total, dtype=self._dtype, device=self.device)
+            esz = flat.element_size()
+            rc = C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(flat.data_ptr()), ptr, C.c_size_t(esz * total), C.c_int(3))
+            if rc != 0:
+                raise _lib.VnlError(f"hipMemcpy failed: {rc}")
+            flat = flat.cpu()
+        else:
+            ct = C.c_double if self._dtype == torch.float64 else C.c_float
+            flat = torch.from_numpy(np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(total,)).copy())
+        return flat.view(self.num_envs, cnt.value)
 
     def __del__(self):
         try:

@@ -145,7 +145,13 @@ class EvalWrapper(Wrapper):
 
 def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None,
          reset_info_on_autoreset: bool = False) -> Wrapper:
-    """brax.envs.training.wrap minus the VmapWrapper (natively batched env)."""
+    """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
+
+    `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
+    num_envs and rng): its result goes to `env.with_domain`, a NEW env with per-env model parameters (RodentTracking.
+    with_domain: cg_friction, act_gain, dof_damping, dof_armature).  The caller's env is left as it is."""
     if randomization_fn is not None:
-        raise NotImplementedError("domain randomisation is outside the hot path")
+        if not hasattr(env, "with_domain"):
+            raise ValueError(f"{type(env).__name__} has no with_domain: domain randomisation needs a tracking env of this library")
+        env = env.with_domain(randomization_fn(env.sys))
     return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset)

@@ -98,6 +98,16 @@ def _dist_info():
     return None, 0, 1
 
 
+def bind_randomization(randomization_fn, num_envs: int, seed: int):
+    """The reference's binding of a `randomization_fn` (train.py:197-202, 416-420): `num_envs` and a generator of its own
+    seeded from `seed` alone -- the training env's is the same on every rank, as the reference's is on every device.
+    Returns `sys -> domain` for envs.wrappers.wrap, or None."""
+    if randomization_fn is None:
+        return None
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    return functools.partial(randomization_fn, num_envs=int(num_envs), rng=g)
+
+
 def train(
     environment,
     num_timesteps: int,
@@ -147,7 +157,13 @@ def train(
     autograd through the op-by-op loss (hipBLASLt), "auto" = hip on a HIP device for the networks of
     make_intention_ppo_networks.
 
-    `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
+    `randomization_fn(sys: CompiledModel, num_envs: int, rng: torch.Generator) -> dict` (domain randomisation, brax's
+    keyword): returns per-env values {field: (num_envs, n)} of some of cg_friction, act_gain, dof_damping, dof_armature
+    (RodentTracking.with_domain), drawn once and fixed for the run.  The training env gets num_envs = the per-rank batch and
+    a generator seeded from `seed` (the same on every rank), the eval env num_eval_envs and a generator of the eval seed
+    (bind_randomization).
+
+        `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
     ~500 launches of microsecond kernels and purely launch-bound.
     """
@@ -172,7 +188,8 @@ def train(
     g_eval = torch.Generator(device="cpu").manual_seed(seed * 31 + 7)
 
     env = env_wrappers.wrap(environment, episode_length=episode_length, action_repeat=action_repeat,
-                            randomization_fn=randomization_fn, reset_info_on_autoreset=reset_info_on_autoreset)
+                            randomization_fn=bind_randomization(randomization_fn, local_envs, seed),
+                            reset_info_on_autoreset=reset_info_on_autoreset)
     env_state = env.reset(g_env)
 
     normalize = (lambda x, y: x)
@@ -532,6 +549,7 @@ def train(
                 raise ValueError(f"eval_env has {eval_env.unwrapped.num_envs} envs, num_eval_envs = {num_eval_envs}")
             eval_env = eval_env.unwrapped.with_num_envs(num_eval_envs)
         ev_wrapped = env_wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat,
+                                       randomization_fn=bind_randomization(randomization_fn, num_eval_envs, seed * 31 + 7),
                                        reset_info_on_autoreset=reset_info_on_autoreset)
         evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval),
                                      num_eval_envs=num_eval_envs, episode_length=episode_length,
