@@ -235,8 +235,9 @@ def test_ant_env_newton_float64_build_matches_oracle():
 
 @pytest.mark.gpu
 def test_ant_env_newton_on_gpu():
-    """The Newton branch of EnvWave::solve on the device: one control step against the oracles following the product's
-    line-search decisions (same bounds as the CG test above) and three more steps finite and deterministic."""
+    """The Newton branch of EnvWave::solve (tree-sparse Hessian) on the device: one control step against the oracles
+    following the product's line-search decisions (same bounds as the CG test above) and three more steps finite and
+    deterministic."""
     B = 256
     env = _env(B, device="cuda:0", params=NEWTON)
     rng = np.random.default_rng(3)

@@ -1,11 +1,10 @@
-"""Newton solver with the tree-sparse Hessian (EnvWaveT::newton_hessian_tree / newton_solve_tree, csrc/vnl_body.h): the route
-that models too large for the dense Hessian in LDS take -- the rodent (nv 73, nefc 303) -- and that the blob scalar
-`newton_route = 2` forces on the small ones.
+"""Newton solver with the tree-sparse Hessian (EnvWaveT::newton_hessian / newton_solve, csrc/vnl_body.h), the one Newton
+solver of the library: the rodent (nv 73, nefc 303), the ant and the humanoid.
 
 CPU tier: the float64 host build of the product source against the dense float64 oracle (whose Newton branch has no size
-limit), the assembled Hessian against a NumPy one, the forced route on the ant and the humanoid.  GPU tier: the rodent and the
-ant on the device against the float64 / float32 oracles following the product's decisions, determinism, graph capture and a
-short training run."""
+limit), the assembled Hessian against a NumPy one, the ant and the humanoid.  GPU tier: the rodent on the device against the
+float64 / float32 oracles following the product's decisions, determinism, graph capture and a short training run (the ant's
+Newton on the device: tests/test_ant_env.py::test_ant_env_newton_on_gpu)."""
 import copy
 import functools
 
@@ -22,12 +21,10 @@ from vnl_brax_imitation_amd.model import mjcf
 CONFIGS = [(6, 6), (1, 4)]  # CG's counts, and the reference's Newton counts (configs/env_config.yaml:16-21)
 
 
-def newton_model(iterations, ls_iterations, route=None, base=None):
+def newton_model(iterations, ls_iterations, base=None):
     """A copy of the compiled model with the Newton options set, as envs/rodent.py _load_model sets them."""
     m = copy.deepcopy(base if base is not None else H.model())
     m.scalars.update(solver_newton=1, iterations=iterations, ls_iterations=ls_iterations)
-    if route is not None:
-        m.scalars["newton_route"] = route
     return m
 
 
@@ -76,7 +73,7 @@ def test_rodent_newton_takes_the_tree_sparse_route():
     env.reset(0)
     assert env.scratch("newton_LD").shape == (1, 1119) and env.scratch("newton_LDiagInv").shape == (1, 73)  # nM, nv
     with pytest.raises(Exception):
-        env.scratch("newton_efc_J")  # no dense Jacobian on this route
+        env.scratch("newton_efc_J")  # no dense Jacobian
     lds = int(env.dims.workspace_floats_per_env) * 4
     assert lds <= 32 * 1024, lds  # five workgroups per CU (160 KiB of LDS)
 
@@ -128,57 +125,50 @@ def test_rodent_newton_tree_hessian_assembly():
             j = par[j]
 
 
-def _ant_env(B, route=None, device="cpu"):
+def _ant_env(B):
     from test_ant_env import ANT_NPZ, NEWTON, _clip
 
     m = mjcf.CompiledModel.load(ANT_NPZ)
-    if route is not None:
-        m.scalars["newton_route"] = route
-    import contextlib
-
-    with (H.hostsim_backend("double") if device == "cpu" else contextlib.nullcontext()):
+    with H.hostsim_backend("double"):
         return envs.get_environment("ant", params=NEWTON, clip_length=60, episode_length=20, reference_clip=_clip(m), model=m,
-                                    num_envs=B, device=device)
+                                    num_envs=B, device="cpu")
 
 
-def _humanoid_env(B, route=None):
+def _humanoid_env(B):
     from test_humanoid import _clip, _model
     from vnl_brax_imitation_amd.envs.humanoid import HumanoidTracking
 
-    m = newton_model(1, 4, route=route, base=_model())
+    m = newton_model(1, 4, base=_model())
     with H.hostsim_backend("double"):
         return HumanoidTracking(dict(solver="newton", iterations=1, ls_iterations=4), clip_length=60, episode_length=20,
                                 reference_clip=_clip(m), model=m, num_envs=B, device="cpu")
 
 
 @pytest.mark.parametrize("which", ["ant", "humanoid"])
-def test_forced_tree_route_on_small_models(which):
-    """newton_route = 2 on the ant (its welded bodies folded) and the humanoid (eulerdamp off): four control steps against
-    the dense route (newton_route absent) and the oracle."""
+def test_small_models_newton_float64_build_matches_oracle(which):
+    """The ant (its welded bodies folded) and the humanoid (eulerdamp off) with Newton 1 / 4: four control steps against the
+    oracle, whose dense Cholesky is the independent check of the tree-sparse factorisation."""
     from test_ant_env import _oracle
 
     B = 6
-    make = _ant_env if which == "ant" else _humanoid_env
-    tree, dense = make(B, route=2), make(B)
-    tree.debug(True), dense.debug(True)
-    nu, nq = tree.action_size, int(tree.sys.scalars["nq"])
+    env = (_ant_env if which == "ant" else _humanoid_env)(B)
+    env.debug(True)
+    nu, nq = env.action_size, int(env.sys.scalars["nq"])
     sf = np.random.default_rng(5).integers(0, 30, B).astype(np.int32)
-    st_t, st_d = (e.reset(start_frame=torch.from_numpy(sf)) for e in (tree, dense))
-    tree.scratch("newton_LD"), dense.scratch("newton_efc_J")  # each env runs the route it was asked for
-    o = _oracle(dense)
+    st = env.reset(start_frame=torch.from_numpy(sf))
+    o = _oracle(env)
     ost = o.env_reset(sf, np.zeros((B, nq)))
     rng = np.random.default_rng(4)
     moved = 0.0
     for _ in range(4):
         a = np.clip(0.5 * rng.standard_normal((B, nu)), -1, 1)
-        st_t, st_d = tree.step(st_t, torch.from_numpy(a)), dense.step(st_d, torch.from_numpy(a))
+        st = env.step(st, torch.from_numpy(a))
         o.env_step(ost, a)
         for k in ("qpos", "qvel", "qacc_warmstart"):
-            x_t, x_d = getattr(st_t.pipeline_state, k).numpy(), getattr(st_d.pipeline_state, k).numpy()
-            assert H.scaled_err(x_t, x_d) < 1e-9, (k, H.scaled_err(x_t, x_d))
-            assert H.scaled_err(x_t, ost[k]) < 1e-9, (k, H.scaled_err(x_t, ost[k]))
-        assert np.array_equal(st_t.done.numpy(), ost["done"])
-        moved = max(moved, float(np.abs(st_t.pipeline_state.qvel.numpy()).max()))
+            x = getattr(st.pipeline_state, k).numpy()
+            assert H.scaled_err(x, ost[k]) < 1e-9, (k, H.scaled_err(x, ost[k]))
+        assert np.array_equal(st.done.numpy(), ost["done"])
+        moved = max(moved, float(np.abs(st.pipeline_state.qvel.numpy()).max()))
     assert moved > 1e-2
 
 
@@ -203,13 +193,21 @@ def test_public_constructors_accept_newton_for_the_rodent():
     assert torch.isfinite(outs[0]).all() and all(torch.equal(outs[0], o) for o in outs[1:])
 
 
-def test_route_errors_are_loud():
-    from vnl_brax_imitation_amd import _lib
-
-    with pytest.raises(_lib.VnlError, match="dense Newton route"):
-        _rodent(1, newton_model(1, 4, route=1))  # the dense Hessian of the rodent does not fit LDS
-    with pytest.raises(_lib.VnlError, match="newton_route"):
-        _rodent(1, newton_model(1, 4, route=3))
+def test_small_models_newton_takes_the_tree_sparse_hessian():
+    """The ant and the humanoid run Newton on the tree-sparse Hessian: its factor and pivots in the debug image, no dense
+    Jacobian."""
+    for make in (_ant_env, _humanoid_env):
+        env = make(1)
+        env.debug(True)
+        env.reset(start_frame=torch.zeros(1, dtype=torch.int32))
+        nv, par, nM = int(env.sys.scalars["nv"]), env.sys.dof_parentid, 0
+        for i in range(nv):  # qM's tree-sparse entries: one per ancestor of each dof, itself included
+            j = i
+            while j >= 0:
+                nM, j = nM + 1, par[j]
+        assert env.scratch("newton_LD").shape == (1, nM) and env.scratch("newton_LDiagInv").shape == (1, nv)
+        with pytest.raises(Exception):
+            env.scratch("newton_efc_J")  # no dense Jacobian
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU tier
@@ -312,23 +310,3 @@ def test_rodent_newton_short_training_on_gpu():
     for k in ("training/total_loss", "training/v_loss", "training/policy_loss"):
         assert np.isfinite(m[k]), (k, m[k])
     assert torch.isfinite(flat).all()
-
-
-@pytest.mark.gpu
-def test_ant_forced_tree_route_on_gpu():
-    """The ant with newton_route = 2 on the device: the bounds of test_ant_env_newton_on_gpu."""
-    from test_ant_env import _oracle
-
-    B = 256
-    env = _ant_env(B, route=2, device="cuda:0")
-    rng = np.random.default_rng(3)
-    sf, noise = np.zeros(B, np.int32), np.zeros((B, 15), np.float32)
-    act = np.clip(0.5 * rng.standard_normal((B, 8)), -1, 1).astype(np.float32)
-    o64, o32 = _oracle(env, "f64"), _oracle(env, "f32")
-    st, err, dev, rep, ost = P.control_step_follow(env, o64, o32, sf, noise, act)
-    print("\n[ant env, Newton 1/4, tree-sparse route, 256 envs] " +
-          ", ".join(f"{k}: max {v.max():.2e} median {np.median(v):.2e}" for k, v in err.items()))
-    P.check_control_step(err, dev, rep, max_flipped=B // 8)
-    causes = P.flip_causes(rep)
-    assert int(causes["other"].sum()) <= max(2, B // 50), causes
-    print("   vs the natural oracle:", P.natural_check(st, o64, o32, act))

@@ -649,18 +649,8 @@ struct EnvWaveT {
     // reads were an L2 round trip in the middle of a serial chain
     VNL_FOR(i, MI(nv)) s[LO(LD) + madr(i)] += par<P_ARM>(i) + diag_scale * par<P_DAMP>(i);
     VNL_SYNC();
-    if (MI(solver_newton) == 2 && diag_scale == vreal(0.)) {  // qM in its own layout: the tree-sparse Newton route's Hessian and M * search
+    if (MI(solver_newton) && diag_scale == vreal(0.)) {  // a copy of qM in its own layout: the Newton solver's Hessian and M * search
       VNL_FOR(e, MI(nM)) s[LO(newt_M) + e] = s[LO(LD) + e];
-      VNL_SYNC();
-    } else if (MI(solver_newton) && diag_scale == vreal(0.)) {  // dense symmetric copy of qM: the Newton solver's Hessian and M * search
-      const int nv = MI(nv);
-      VNL_FOR(k, nv * nv) s[LO(newt_M) + k] = vreal(0.);
-      VNL_SYNC();
-      VNL_FOR(e, MI(nM)) {
-        const int i = m.M_row[e], j = anc_of(e);
-        const vreal v = s[LO(LD) + e];
-        s[LO(newt_M) + i * nv + j] = v, s[LO(newt_M) + j * nv + i] = v;
-      }
       VNL_SYNC();
     }
     VNL_PROF(6);
@@ -672,8 +662,8 @@ struct EnvWaveT {
   // table (ordered by a+c, so a prefix of it enumerates any depth).  The division of row k by its
   // pivot is deferred to one final pass (row k is never touched again after iteration k).
   VNL_HD void factor_lds() const { factor_lds(LO(LD), LO(dinv), false); }
-  // (LDb / dinvb: where the matrix sits and where its reciprocal pivots go -- LO(LD), or the Newton Hessian of the tree-sparse
-  // route; guard: a pivot that is not positive is replaced by VNL_MINVAL, as the dense Newton route's Cholesky does)
+  // (LDb / dinvb: where the matrix sits and where its reciprocal pivots go -- LO(LD), or the Newton Hessian; guard: a pivot
+  // that is not positive is replaced by VNL_MINVAL, as the oracle's Newton Cholesky does)
   VNL_HD void factor_lds(int LDb, int dinvb, bool guard) const {
     // (A column-per-lane variant that keeps the pivot row in registers and broadcasts it with
     // v_readlane was measured 2x slower: one LDS round trip in flight per step.  What matters is the
@@ -815,8 +805,8 @@ struct EnvWaveT {
     factor_rows_at<NSET, MAXD, SOLVE, MAXD1>(with_loop, rhs, LO(LD), LO(dinv), (LO(Ma) + 3) & ~3);
   }
   // (LDb / dinvb / scb: the matrix, its reciprocal pivots and the scratch lines -- qM's factor in LO(LD) with the lines in the
-  // dead CG vectors, or the tree-sparse Newton Hessian with the lines in the pool (newton_factor_tree); GUARD: a pivot that is
-  // not positive is replaced by VNL_MINVAL, as the dense Newton route's Cholesky does)
+  // dead CG vectors, or the Newton Hessian with the lines in the pool (newton_factor); GUARD: a pivot that is not positive is
+  // replaced by VNL_MINVAL, as the oracle's Newton Cholesky does)
   template <int NSET, int MAXD, bool SOLVE = false, int MAXD1 = MAXD, bool GUARD = false>
   VNL_HD void factor_rows_at(bool with_loop, int rhs, int LDb, int dinvb, int scb) const {
     static_assert(MAXD % 12 == 0 || MAXD == 16, "columns are processed in chunks of 12 (or 16)");
@@ -1991,98 +1981,15 @@ struct EnvWaveT {
   }
 
   // ---- Newton solver (solver.py _update_gradient, SolverType.NEWTON): Mgrad = H^-1 grad with the Hessian of the cost at the
-  // current active set, H = qM + J' diag(efc_D * active) J.  Two routes (build_dev_model picks one, m.solver_newton):
-  //   1, dense: H formed and Cholesky-factorised dense in LDS, efc_J materialised once per substep (small models: the
-  //      reference selects Newton for the ant, nv 14, configs/env_config.yaml:16-21);
-  //   2, tree-sparse (newton_*_tree below): H has qM's sparsity, so it lives in the qLD layout and is factorised by the
-  //      same tree-sparse L'DL (any model, the rodent's 73 dofs / 303 rows among them).
-  VNL_HD void newton_jacobian() const {
-    const int nv = MI(nv);
-    V3 n = v3(m.pnx, m.pny, m.pnz);
-    VNL_FOR(k, MI(nefc) * nv) s[LO(newt_J) + k] = vreal(0.);
-    VNL_SYNC();
-    VNL_FOR(r, MI(nlimit)) s[LO(newt_J) + r * nv + m.lim_dof[r]] = copysign(vreal(1.), s[LO(efc_D) + r]);
-    VNL_FOR(q, MI(ncon) * nv) {
-      const int c = q / nv, d = q - c * nv, g = m.con_geom[c] & 0xff, r0 = MI(nlimit) + 4 * c;
-      if (s[LO(efc_D) + r0] == vreal(0.)) continue;
-      const int* seg = m.body_pathseg + 8 * con_body(c);
-      bool on_path = false;
-#pragma unroll
-      for (int k = 0; k < 4; k++) on_path = on_path || (d >= (seg[k] & 0xff) && d < (seg[k] >> 8));
-      if (!on_path) continue;
-      const S6 cd = ld6(LO(cdof) + 6 * d);
-      const V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
-      const V3 pv = cd.l + cross(cd.a, rel);
-      const vreal mu = par<P_MU>(g), jn = dot(n, pv), j1 = dot(t1, pv) * mu, j2 = dot(t2, pv) * mu;
-      s[LO(newt_J) + r0 * nv + d] = jn + j1, s[LO(newt_J) + (r0 + 1) * nv + d] = jn - j1;
-      s[LO(newt_J) + (r0 + 2) * nv + d] = jn + j2, s[LO(newt_J) + (r0 + 3) * nv + d] = jn - j2;
-    }
-    VNL_SYNC();
-  }
-  // x <- H^-1 x (x: a dof vector in LDS); Jaref as it stands decides the active set
-  VNL_HD void newton_solve(int x) const {
-    const int nv = MI(nv), H = LO(newt_H);
-    VNL_FOR(k, nv * nv) {
-      const int i = k / nv, j = k - i * nv;
-      vreal h = s[LO(newt_M) + k];
-      for (int r = 0; r < MI(nefc); r++) {
-        const vreal D = s[LO(efc_D) + r];
-        if (D != vreal(0.) && s[LO(Jaref) + r] < vreal(0.)) h += fabs(D) * s[LO(newt_J) + r * nv + i] * s[LO(newt_J) + r * nv + j];
-      }
-      s[H + k] = h;
-    }
-    VNL_SYNC();
-    // dense Cholesky, lower, column by column (cho_factor): the diagonal by one lane, the column below it one row per lane
-    for (int j = 0; j < nv; j++) {
-      VNL_SERIAL {
-        vreal d = s[H + j * nv + j];
-        for (int k = 0; k < j; k++) d -= s[H + j * nv + k] * s[H + j * nv + k];
-        if (!(d > vreal(0.))) d = VNL_MINVAL;
-        s[H + j * nv + j] = sqrt(d);
-      }
-      VNL_SYNC();
-      VNL_FOR(i, nv) {
-        if (i > j) {
-          vreal t = s[H + i * nv + j];
-          for (int k = 0; k < j; k++) t -= s[H + i * nv + k] * s[H + j * nv + k];
-          s[H + i * nv + j] = t / s[H + j * nv + j];
-        }
-      }
-      VNL_SYNC();
-    }
-    VNL_SERIAL {  // cho_solve: forward and back substitution
-      for (int i = 0; i < nv; i++) {
-        vreal v = s[x + i];
-        for (int k = 0; k < i; k++) v -= s[H + i * nv + k] * s[x + k];
-        s[x + i] = v / s[H + i * nv + i];
-      }
-      for (int i = nv - 1; i >= 0; i--) {
-        vreal v = s[x + i];
-        for (int k = i + 1; k < nv; k++) v -= s[H + k * nv + i] * s[x + k];
-        s[x + i] = v / s[H + i * nv + i];
-      }
-    }
-    VNL_SYNC();
-  }
-  // out = qM v (dense copy): with search = -H^-1 grad the recurrence M s' = -grad + beta M s of the CG route does not hold
-  VNL_HD void newton_mass_mul(int v, int out) const {
-    const int nv = MI(nv);
-    VNL_FOR(i, nv) {
-      vreal acc = vreal(0.);
-      for (int j = 0; j < nv; j++) acc += s[LO(newt_M) + i * nv + j] * s[v + j];
-      s[out + i] = acc;
-    }
-    VNL_SYNC();
-  }
-
-  // Tree-sparse route.  Every constraint row's Jacobian lives on ONE body's path to the root: a limit row on its dof, the four
+  // current active set, H = qM + J' diag(efc_D * active) J, kept tree-sparse in the qLD layout.
+  // Every constraint row's Jacobian lives on ONE body's path to the root: a limit row on its dof, the four
   // pyramid rows of a contact on the path of the body whose geom touches the plane (J(r, d) = cdof_d . w_r with the row's
   // wrench w_r = [rel x p_r ; p_r], p_r = n +- mu t1 / n +- mu t2).  So J_r' D_r J_r is nonzero only where both dofs lie on
   // that path, i.e. one is an ancestor of the other: H keeps qM's layout, entry (i, j) with j an ancestor of i (or i itself)
   //     H(i, j) = qM(i, j) + u_i . cdof_j (+ D of dof i's active limit row on the diagonal),
   //     u_i = sum over the active rows r of the contacts whose path holds dof i of D_r w_r (w_r . cdof_i),
-  // -- one lane per row of H, no J, no fill-in.  Active: D != 0 and Jaref < 0 (newton_solve, oracle slv_update_gradient).
-  VNL_HD void newton_hessian_tree() const {
+  // -- one lane per row of H, no J, no fill-in.  Active: D != 0 and Jaref < 0 (oracle slv_update_gradient).
+  VNL_HD void newton_hessian() const {
     const int Hb = LO(newt_H);
     const V3 n = v3(m.pnx, m.pny, m.pnz);
     const unsigned char* act = (const unsigned char*)(s + LO(act_list));
@@ -2124,13 +2031,13 @@ struct EnvWaveT {
     VNL_SYNC();
   }
   // x <- H^-1 x: H assembled at the active set as Jaref stands, factorised in place (L'DL, pivots guarded), the factor inverted
-  // (build_dev_model admits this route only where the register-resident inversion applies) and applied like qM's
+  // (build_dev_model admits a Newton model only where the register-resident inversion applies) and applied like qM's
   // (solve_inplace: tmp2 is its scratch; Ma .. search, the scratch of qM's own factorisation routines, are live here)
-  VNL_HD void newton_solve_tree(int x) const {
+  VNL_HD void newton_solve(int x) const {
     const int Hb = LO(newt_H), dinvb = LO(newt_H) + MI(nM);
-    newton_hessian_tree();
+    newton_hessian();
     VNL_PROF(31);
-    newton_factor_tree(Hb, dinvb);
+    newton_factor(Hb, dinvb);
     VNL_PROF(32);
     invert_factor(Hb);
     VNL_PROF(33);
@@ -2138,7 +2045,7 @@ struct EnvWaveT {
   }
   // L'DL of the Hessian in place: the register-resident row elimination of qM's factor() with its scratch lines in the part of
   // the pool that the contact-wrench / dof prefix sums use (dead between constraint_force and the next jac_mul), else the LDS form
-  VNL_HD void newton_factor_tree(int Hb, int dinvb) const {
+  VNL_HD void newton_factor(int Hb, int dinvb) const {
     const int nv = MI(nv), md = MI(max_depth);
     const int scb = (LO(P) + 3 * MI(nefc) + 3) & ~3, room = LO(smooth) - scb;
     if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16 && VNL_FAC_LINES * (16 + 4) <= room)
@@ -2149,8 +2056,9 @@ struct EnvWaveT {
       factor_rows_at<VNL_ROWSETS_2, 36, false, 16, true>(true, 0, Hb, dinvb, scb);
     else factor_lds(Hb, dinvb, true);
   }
-  // out = qM v with qM's tree-sparse entries (symmetric: row i's own entries, then column i in the rows of i's descendants)
-  VNL_HD void newton_mass_mul_tree(int v, int out) const {
+  // out = qM v with qM's tree-sparse entries (symmetric: row i's own entries, then column i in the rows of i's descendants):
+  // with search = -H^-1 grad the recurrence M s' = -grad + beta M s of the CG route does not hold
+  VNL_HD void newton_mass_mul(int v, int out) const {
     const int Mb = LO(newt_M);
     VNL_FOR(i, MI(nv)) {
       const int adr = madr(i), dep = eadr(i) - adr, nd = ndesc(i);
@@ -2159,14 +2067,6 @@ struct EnvWaveT {
       s[out + i] = acc;
     }
     VNL_SYNC();
-  }
-  VNL_HD void newton_solve_any(int x) const {
-    if (MI(solver_newton) == 2) newton_solve_tree(x);
-    else newton_solve(x);
-  }
-  VNL_HD void newton_mass_mul_any(int v, int out) const {
-    if (MI(solver_newton) == 2) newton_mass_mul_tree(v, out);
-    else newton_mass_mul(v, out);
   }
 
   // solver.solve (CG / Newton).  One env per wave: the while loops run with this env's own trip counts.
@@ -2211,12 +2111,8 @@ struct EnvWaveT {
     gg = vnl_wave_sum(gg);
     VNL_SYNC();
     const bool newton = MI(solver_newton) != 0;
-    if (newton) {
-      if (MI(solver_newton) == 1) fresh().newton_jacobian();
-      fresh().newton_solve_any(LO(Mgrad));
-    } else {
-      fresh().solve_inplace(LO(Mgrad));
-    }
+    if (newton) fresh().newton_solve(LO(Mgrad));
+    else fresh().solve_inplace(LO(Mgrad));
     VNL_FOR(d, nv) {
       const vreal mg = s[LO(Mgrad) + d], gr = s[LO(grad) + d];
       s[LO(search) + d] = -mg;
@@ -2225,7 +2121,7 @@ struct EnvWaveT {
     }
     ss = vnl_wave_sum(ss), gp = vnl_wave_sum(gp);
     VNL_SYNC();
-    if (newton) fresh().newton_mass_mul_any(LO(search), LO(mv));
+    if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
     VNL_PROF(15);
 
     for (int it = 0; it < MI(iterations); it++) {
@@ -2287,7 +2183,7 @@ struct EnvWaveT {
       d1 = vnl_wave_sum(d1), gg = vnl_wave_sum(gg);
       VNL_SYNC();
       VNL_PROF(23);
-      if (newton) fresh().newton_solve_any(LO(tmp));
+      if (newton) fresh().newton_solve(LO(tmp));
       else fresh().solve_inplace(LO(tmp));
       VNL_PROF(24);
       vreal d2 = vdot(LO(grad), LO(tmp));
@@ -2305,7 +2201,7 @@ struct EnvWaveT {
       }
       ss = vnl_wave_sum(ss);
       VNL_SYNC();
-      if (newton) fresh().newton_mass_mul_any(LO(search), LO(mv));
+      if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
       VNL_PROF(25);
     }
   }
@@ -2378,7 +2274,7 @@ struct EnvWaveT {
     VNL_PROF(1);
     int cvel = fresh().bias_forces();
     if (factor_pair_ok()) {
-      // (the factors come from the composite inertias directly; the matrix itself only where the Newton solver wants its dense copy)
+      // (the factors come from the composite inertias directly; the matrix itself only where the Newton solver wants its copy)
       if (MI(solver_newton)) fresh().mass_matrix(vreal(0.));
       else fresh().tree_accumulate(LO(P), 10);
       VNL_PROF(5);

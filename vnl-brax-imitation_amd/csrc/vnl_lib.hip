@@ -329,20 +329,9 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   d.ncg = (int)S("ncg"), d.ncon = (int)S("ncon"), d.nlimit = (int)S("nlimit"), d.nefc = (int)S("nefc");
   d.iterations = (int)S("iterations"), d.ls_iterations = (int)S("ls_iterations"), d.eulerdamp = (int)S("eulerdamp");
   d.dt = (vreal)S("timestep"), d.tolerance = (vreal)S("tolerance"), d.ls_tolerance = (vreal)S("ls_tolerance");
-  // Newton (reference configs/env_config.yaml:16-21): the Hessian M + J' D J is formed and factorised DENSE in LDS for small
-  // models (nv <= 48, nefc <= 160: the ant, the humanoid), in qM's tree-sparse layout for larger ones (the rodent).  The optional
-  // blob scalar newton_route forces a route (0 or absent: automatic, 1 dense, 2 tree-sparse; the oracle ignores it).
-  const double route_s = S("newton_route");
-  const int route = route_s == route_s ? (int)route_s : 0;
-  if (route < 0 || route > 2 || route_s == route_s && route_s != (double)route)
-    return fail(VNL_ERR_BLOB, "newton_route must be 0 (automatic), 1 (dense) or 2 (tree-sparse)");
-  d.solver_newton = 0;
-  if (S("solver_newton") != 0) {
-    const bool small = d.nv <= 48 && d.nefc <= 160;
-    if (route == 1 && !small)
-      return fail(VNL_ERR_UNSUPPORTED, "the dense Newton route is implemented for small models (nv <= 48, nefc <= 160): dense Hessian in LDS");
-    d.solver_newton = (route == 1 || (route == 0 && small)) ? 1 : 2;
-  }
+  // Newton (reference configs/env_config.yaml:16-21): the Hessian M + J' D J is formed and factorised in qM's tree-sparse layout
+  // (the checks at the end of this function refuse a model that does not admit it)
+  d.solver_newton = S("solver_newton") != 0;
   d.dbg_stage = 0, d.dbg_count = 0;
 #ifdef VNL_STAGE_KNOBS  // diagnostic library only: the product library reads no environment variables
   if (const char* dbg = getenv("VNL_DBG_REPEAT")) sscanf(dbg, "%d:%d", &d.dbg_stage, &d.dbg_count);
@@ -761,8 +750,8 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   }
 #undef UPF
 #undef UPI
-  if (d.solver_newton == 2) {
-    // The tree-sparse Newton route (EnvWaveT::newton_hessian_tree) relies on every constraint row's Jacobian living on ONE
+  if (d.solver_newton) {
+    // The Newton solver's tree-sparse Hessian (EnvWaveT::newton_hessian) relies on every constraint row's Jacobian living on ONE
     // body's path to the root: a limit row on the single dof of its hinge (one limit row per dof: dof_limrow holds one), a
     // contact's rows on the path of the one dynamic body whose geom touches the plane.  Its factor is inverted in registers
     // (EnvWaveT::invert_rows): the depth bounds of that form must hold.
@@ -771,15 +760,15 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
       if (I("jnt_limited")[j] && I("jnt_type")[j] == VNL_JNT_HINGE) {
         const int dd = I("jnt_dofadr")[j];
         if (dd < 0 || dd >= nv || ++nlim[dd] > 1)
-          return fail(VNL_ERR_UNSUPPORTED, "tree-sparse Newton route: a limit row does not act on exactly one dof of its own");
+          return fail(VNL_ERR_UNSUPPORTED, "Newton solver: a limit row does not act on exactly one dof of its own");
       }
     for (int g = 0; g < ng; g++) {
       const int b = I("cg_bodyid")[g];
-      if (b < 0 || b >= nb) return fail(VNL_ERR_UNSUPPORTED, "tree-sparse Newton route: a contact is not attached to one dynamic body");
+      if (b < 0 || b >= nb) return fail(VNL_ERR_UNSUPPORTED, "Newton solver: a contact is not attached to one dynamic body");
     }
     const int deep1 = d.fac_nleaf >> 8;
     if (!(d.max_depth < 36 && (nv <= 64 || (nv <= 128 && deep1 < 16))))
-      return fail(VNL_ERR_UNSUPPORTED, "tree-sparse Newton route: dof tree too deep for the register-resident inversion of the "
+      return fail(VNL_ERR_UNSUPPORTED, "Newton solver: dof tree too deep for the register-resident inversion of the "
                                        "Hessian's factor (max depth < 36; rows 64 .. of depth < 16; nv <= 128)");
   }
   return VNL_OK;
@@ -807,10 +796,8 @@ static void layout(vnl_env* env) {
   sec("tab_body", L.tab_body, L.tab_jump - L.tab_body), sec("tab_jump", L.tab_jump, L.tab_lvl - L.tab_jump);
   sec("tab_lvl", L.tab_lvl, L.act_list - L.tab_lvl);
   sec("act_list", L.act_list, vnl_words(4 * (long)((d.ncon + 3) / 4) + 8 + 2 * VNL_LIVE_MAX));
-  if (d.solver_newton == 2) {  // tree-sparse route: qM, and the Hessian's inverted L'DL factor and pivots, in the qLD layout
+  if (d.solver_newton) {  // qM, and the Hessian's inverted L'DL factor and pivots, in the qLD layout
     sec("newton_qM", L.newt_M, d.nM), sec("newton_LD", L.newt_H, d.nM), sec("newton_LDiagInv", L.newt_H + d.nM, d.nv);
-  } else if (d.solver_newton) {
-    sec("newton_qM", L.newt_M, d.nv * d.nv), sec("newton_H", L.newt_H, d.nv * d.nv), sec("newton_efc_J", L.newt_J, d.nefc * d.nv);
   }
 #ifdef VNL_PROFILE
   sec("prof", L.prof, 2 * (VNL_NPROF + 1));

@@ -35,9 +35,8 @@ typedef VNL_REAL vreal;
 struct DevModel {
   int nq, nv, nu, nbody, njnt, ncg, ncon, nlimit, nefc, nM;
   int iterations, ls_iterations, eulerdamp, root_free, max_depth, jump_rounds;
-  int solver_newton; /* opt.solver == NEWTON (reference configs/env_config.yaml:16-21): 0 CG, 1 Newton with the dense Hessian in
-                        LDS (small models: nv <= 48, nefc <= 160), 2 Newton with the tree-sparse Hessian (any model; vnl_lib.hip:
-                        build_dev_model picks the route) */
+  int solver_newton; /* opt.solver == NEWTON (reference configs/env_config.yaml:16-21): 0 CG, 1 Newton with the tree-sparse
+                        Hessian */
   int fac_steps; /* number of steps of the factorisation schedule */
   int fac_nleaf; /* low byte: leaf dofs of the tree if <= VNL_FAC_LINES (factor_rows can then carry and solve a right-hand
                     side), else 0; bits 8..: depth of the deepest of the rows 64 .. (second lane set) */
@@ -123,9 +122,8 @@ struct WsLayout {
   int tab_anc, tab_madr, tab_body, tab_jump, tab_lvl; /* 8/16-bit index tables staged in LDS */
   int act_list;         /* ncon bytes: contacts with D != 0, then their count (int) */
   int pair_room;        /* elements from LD to the part of the pool that stays live across the factorisation (cvel): (kept for the layout's stability; the articulated-body factorisation needs 12 nv elements of the pool below cvel) */
-  int newt_M, newt_H, newt_J; /* Newton solver only.  Dense route (solver_newton 1): dense qM (nv^2), Hessian / its Cholesky factor
-                                 (nv^2), dense efc_J (nefc x nv).  Tree-sparse route (2): qM in the qLD layout (nM), the Hessian's
-                                 inverted L'DL factor in that layout (nM) followed by its reciprocal pivots (nv); newt_J unused */
+  int newt_M, newt_H; /* Newton solver only: qM in the qLD layout (nM), the Hessian's inverted L'DL factor in that layout (nM)
+                         followed by its reciprocal pivots (nv) */
   int total;
 };
 
@@ -174,13 +172,8 @@ constexpr WsLayout vnl_make_layout(const VnlDims& d) {
   L.tab_jump = sec(vnl_words((long)(d.jump_rounds > 0 ? d.jump_rounds : 1) * d.nbody));
   L.tab_lvl = sec(vnl_words((long)d.nv + d.max_depth + 2));
   L.act_list = sec(vnl_words(4 * (long)((d.ncon + 3) / 4) + 8 + 2 * VNL_LIVE_MAX)); /* active contacts | their count | existing rows: count, list */
-  L.newt_M = L.newt_H = L.newt_J = 0;
-  if (d.solver_newton == 2) {
-    L.newt_M = sec(d.nM), L.newt_H = sec(d.nM + d.nv);
-  } else if (d.solver_newton) {
-    L.newt_M = sec(d.nv * d.nv), L.newt_H = sec(d.nv * d.nv);
-    L.newt_J = sec(d.nefc * d.nv);
-  }
+  L.newt_M = L.newt_H = 0;
+  if (d.solver_newton) L.newt_M = sec(d.nM), L.newt_H = sec(d.nM + d.nv);
   if (VNL_NPROF_SLOTS) {
     o = (o + 1) & ~1;
     L.prof = sec(VNL_NPROF_SLOTS);

@@ -3,8 +3,8 @@
 What differs from the rodent env (selected by the env flags of include/vnl.h, VNL_ENV_*):
   * model assets/ant.xml through brax's `mjcf.load`, which fuses the four joint-less leg bodies into the torso: the env
     sees 10 bodies (world, torso, aux_i, ankle bodies) -- here the tracked-body list; implicit damping
-    off (ant.py:47); the reference's config asks for the Newton solver, this library has CG only (same constraint model,
-    `H = M + J'DJ` Cholesky instead of the `M^-1` preconditioner) and says so at construction;
+    off (ant.py:47); the solver follows `params["solver"]`: the reference's config asks for Newton (same constraint model,
+    `H = M + J'DJ` instead of CG's `M^-1` preconditioner), which runs on the tree-sparse Hessian of every Newton model;
   * observation = [reference-trajectory features | qpos | qvel] (ant.py:293-338), the features built from the
     UN-incremented frame counter (ant.py:178), without the appendage block;
   * every reward term from the state BEFORE the step (ant.py:180), `ract` from the action (ant.py:277), weights 0.05 /
