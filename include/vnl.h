@@ -141,6 +141,11 @@ typedef struct vnl_dims {
                                        parents; every one of the nbody bodies still has its row of xpos / xquat */
   int32_t kernel_specialised;       /* 1: the env runs the kernels specialised at compile time for its dimensions (the reference's
                                        rodent); 0: the generic kernels */
+  int32_t factor_route;             /* the routes of the factorisations, chosen for the model at env creation: a nibble each,
+                                       bits 0..3 qM's factor, 4..7 its inverse, 8..11 the Newton Hessian's factor (0: CG), in
+                                       each 1 LDS-resident, 2 / 3 rows in registers (max depth < 16 / 36), 4 rows in registers
+                                       over two lane sets (nv <= 128); bits 12..15: 0, or the lane sets (1, 2) of the
+                                       articulated-body form that makes both factors of a substep at once (eulerdamp) */
 } vnl_dims;
 
 const char* vnl_last_error(void);

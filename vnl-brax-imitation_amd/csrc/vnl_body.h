@@ -661,7 +661,6 @@ struct EnvWaveT {
   // iteration k run in one parallel region; pair p -> (a, a+c) comes from one universal triangular
   // table (ordered by a+c, so a prefix of it enumerates any depth).  The division of row k by its
   // pivot is deferred to one final pass (row k is never touched again after iteration k).
-  VNL_HD void factor_lds() const { factor_lds(LO(LD), LO(dinv), false); }
   // (LDb / dinvb: where the matrix sits and where its reciprocal pivots go -- LO(LD), or the Newton Hessian; guard: a pivot
   // that is not positive is replaced by VNL_MINVAL, as the oracle's Newton Cholesky does)
   VNL_HD void factor_lds(int LDb, int dinvb, bool guard) const {
@@ -793,28 +792,18 @@ struct EnvWaveT {
   // it (numerators + pivot) in an LDS scratch line; every proper ancestor row a of j then does
   // row_a[c] -= (row_j[a] / D_j) * row_j[c] on its registers, reading row_j as LDS broadcasts.  One
   // wave executes its LDS operations in order, so the scratch line needs no double buffering.
-  // SOLVE: the matrix is only needed to solve ONE system (forward.euler's M + h diag(damping)): the right-hand
-  // side rides along as an extra column (L' w = rhs is eliminated by the very same updates), the factor is
-  // never stored, and x = L^-1 D^-1 w follows by a forward substitution over the depth: the rows of depth c
-  // publish their x once per leaf below them, every deeper row reads "its" ancestor's x at a static offset.
-  // Replaces factor + inversion + two sparse products for that system.
   // MAXD1: column bound of the SECOND lane set (rows 64 .. 127) when there are exactly two: those rows are often
   // shallow (rodent: depth <= 13), and registers for columns they do not have would be dead weight.
-  template <int NSET, int MAXD, bool SOLVE = false, int MAXD1 = MAXD>
-  VNL_HD void factor_rows(bool with_loop = true, int rhs = 0) const {
-    factor_rows_at<NSET, MAXD, SOLVE, MAXD1>(with_loop, rhs, LO(LD), LO(dinv), (LO(Ma) + 3) & ~3);
-  }
   // (LDb / dinvb / scb: the matrix, its reciprocal pivots and the scratch lines -- qM's factor in LO(LD) with the lines in the
-  // dead CG vectors, or the Newton Hessian with the lines in the pool (newton_factor); GUARD: a pivot that is not positive is
-  // replaced by VNL_MINVAL, as the oracle's Newton Cholesky does)
-  template <int NSET, int MAXD, bool SOLVE = false, int MAXD1 = MAXD, bool GUARD = false>
-  VNL_HD void factor_rows_at(bool with_loop, int rhs, int LDb, int dinvb, int scb) const {
+  // dead CG vectors (factor), or the Newton Hessian with the lines in the pool (newton_factor); GUARD: a pivot that is not
+  // positive is replaced by VNL_MINVAL, as the oracle's Newton Cholesky does)
+  template <int NSET, int MAXD, int MAXD1 = MAXD, bool GUARD = false>
+  VNL_HD void factor_rows_at(bool with_loop, int LDb, int dinvb, int sc) const {
     static_assert(MAXD % 12 == 0 || MAXD == 16, "columns are processed in chunks of 12 (or 16)");
     constexpr int CH = MAXD % 12 == 0 ? 12 : 16;
     auto qd = [](int q) constexpr { return (NSET == 2 && q == 1) ? MAXD1 : MAXD; };
     vreal rr[NSET][MAXD], dg[NSET];
     int dep[NSET], last[NSET];
-    const int sc = scb;  // (qM: Ma|grad|Mgrad|search are dead while factorising); VNL_FAC_LINES * (MAXD + 4) floats
 #pragma unroll
     for (int q = 0; q < NSET; q++) {
       int a = (int)lane + q * VNL_LANES;
@@ -830,14 +819,12 @@ struct EnvWaveT {
     // descendants; rows with disjoint subtrees share a step, each with its own scratch line
     // [row numerators (MAXD) | 1/pivot | j | pad], so the chain of dependent steps is the tree height.
     constexpr int LW = MAXD + 4;
-    int ftime[NSET], fpack[NSET];  // fpack: scratch line | one leaf below << 8 | mask of all leaves below << 16
-    vreal bb[NSET], myinv[NSET];   // SOLVE only
+    int ftime[NSET], fslot[NSET];
 #pragma unroll
     for (int q = 0; q < NSET; q++) {
       int a = (int)lane + q * VNL_LANES;
-      fpack[q] = a < MI(nv) ? m.dof_fslot[a] : 0;
+      fslot[q] = a < MI(nv) ? m.dof_fslot[a] : 0;
       ftime[q] = a < MI(nv) ? m.dof_ftime[a] : -1;
-      bb[q] = (SOLVE && a < MI(nv)) ? s[rhs + a] : vreal(0.), myinv[q] = vreal(0.);
     }
     VNL_SYNC();
     VNL_PROF(7);
@@ -849,7 +836,7 @@ struct EnvWaveT {
         bool mine = ftime[q] == step;
         npub += VNL_COUNT(mine);
         if (mine) {
-          int line = sc + (fpack[q] & 0xff) * LW, a = (int)lane + q * VNL_LANES;
+          int line = sc + fslot[q] * LW, a = (int)lane + q * VNL_LANES;
 #pragma unroll
           for (int c0 = 0; c0 < MAXD; c0 += CH) {
             if (c0 < qd(q) && c0 < dep[q]) {
@@ -864,12 +851,7 @@ struct EnvWaveT {
           vreal inv = vnl_recip(dg[q]);
           s[line + MAXD] = inv;
           s[line + MAXD + 1] = vreal(a);  // exact: a < 2^24
-          if constexpr (SOLVE) {
-            s[line + MAXD + 2] = bb[q];
-            myinv[q] = inv;
-          } else {
-            s[dinvb + a] = inv;
-          }
+          s[dinvb + a] = inv;
         }
       }
       VNL_WAVE_FENCE();
@@ -928,37 +910,10 @@ struct EnvWaveT {
               }
             }
             dg[q] -= t * traw;
-            if constexpr (SOLVE) bb[q] -= t * line[MAXD + 2];
           }
         }
       }
       VNL_WAVE_FENCE();
-    }
-    if constexpr (SOLVE) {
-      VNL_SYNC();
-      const int xs = sc;  // [leaf][MAXD] published x values; the scratch lines are no longer needed
-      vreal(&acc)[NSET] = bb;  // (same registers: w is consumed here)
-#pragma unroll
-      for (int q = 0; q < NSET; q++) acc[q] = bb[q] * myinv[q];  // D^-1 w
-#pragma unroll
-      for (int c = 0; c < MAXD; c++) {
-        if (c <= MI(max_depth)) {
-#pragma unroll
-          for (int q = 0; q < NSET; q++) {
-            int a = (int)lane + q * VNL_LANES;
-            if (a < MI(nv) && dep[q] == c) {  // final: all ancestor terms are in
-              s[rhs + a] = acc[q];
-              for (int mk = fpack[q] >> 16; mk != 0; mk &= mk - 1) s[xs + __builtin_ctz(mk) * MAXD + c] = acc[q];
-            }
-          }
-          VNL_WAVE_FENCE();
-#pragma unroll
-          for (int q = 0; q < NSET; q++)
-            if (c < qd(q) && dep[q] > c) acc[q] -= rr[q][c] * myinv[q] * s[xs + ((fpack[q] >> 8) & 0xff) * MAXD + c];
-        }
-      }
-      VNL_SYNC();
-      return;
     }
     VNL_SYNC();
     VNL_PROF(8);
@@ -1054,7 +1009,7 @@ struct EnvWaveT {
       const vreal arm = par<P_ARM>(aa);
       diag[q] = v2r{arm, arm + h * par<P_DAMP>(aa)};
       adrs[q] = madr(aa), dep[q] = eadr(aa) - adrs[q];
-      myline[q] = m.dof_fslot[aa] & 0xff;
+      myline[q] = m.dof_fslot[aa];
       ftime[q] = ok ? m.dof_ftime[aa] : -1;
       mt[q] = m.fac_match + (size_t)aa * nsteps;
       nxt[q] = (ok && nsteps > 0) ? mt[q][0] : 0u;
@@ -1120,13 +1075,9 @@ struct EnvWaveT {
     VNL_PROF(9);
   }
 
-  VNL_HD int vstore() const { return (LO(P) + 3) & ~3; }  // [nv][(V1, V2) x 6]: over crb, below cvel (factor_pair_ok)
-  // where bias_forces leaves cvel for make_constraint: behind cacc / cfrc (pool + 16 nbody) and, where the pool has the room,
-  // behind the store of the V vectors too (with the welded bodies folded away the body arrays are shorter than that store)
-  VNL_HD int cvel_at() const {
-    const int a = LO(P) + 16 * MI(nbody), b = vstore() + 12 * MI(nv);
-    return (b > a && b + 6 * MI(nbody) <= LO(smooth)) ? b : a;
-  }
+  // [nv][(V1, V2) x 6], and where bias_forces leaves cvel for make_constraint (vnl_types.h)
+  VNL_HD int vstore() const { return vnl_vstore(LO(P)); }
+  VNL_HD int cvel_at() const { return vnl_cvel_at(LO(P), LO(smooth), MI(nbody), MI(nv)); }
 
   // Both inverse factors N = L^-1 from the same 6-vectors: walking up from row k, with C = V_k at the start,
   //     N(k, j) = -cdof_j . C,     C += N(k, j) V_j          for the parent j, the grandparent, ..
@@ -1183,49 +1134,34 @@ struct EnvWaveT {
     VNL_SYNC();
   }
 
-  // models whose two factorisations go through factor_aba: the store of the V vectors (12 nv elements from the pool's start) ends
-  // below cvel, which make_constraint still needs, and the six scratch lines fit into the dead vectors Mgrad .. tmp2
-  VNL_HD bool factor_pair_ok() const {
-    const int nv = MI(nv);
-    if (!MI(eulerdamp) || !m.fac_match) return false;
-    return nv <= VNL_ROWSETS_2 * VNL_LANES && vstore() + 12 * nv <= cvel_at() && VNL_FAC_LINES * 16 + 3 <= 6 * nv;
-  }
+  // The dispatchers: each runs the route the host chose for this model (vnl_types.h: VNL_ROUTE_*, vnl_lib.hip: choose_routes).
+  // In a specialised kernel the route is a constant and the routes the model does not take are not compiled.
+  VNL_HD int route(int at) const { return (MI(fac_route) >> at) & 0xf; }
+  // both factorisations of a substep through factor_aba / invert_aba (eulerdamp models whose V store fits below cvel)
+  VNL_HD bool factor_pair_ok() const { return route(VNL_ROUTE_PAIR) != 0; }
   VNL_HD void factor_both(vreal h) const {
-    if (MI(nv) <= VNL_ROWSETS_1 * VNL_LANES) factor_aba<VNL_ROWSETS_1>(h);
+    if (route(VNL_ROUTE_PAIR) == 1) factor_aba<VNL_ROWSETS_1>(h);
     else factor_aba<VNL_ROWSETS_2>(h);
   }
-
+  // qM's L'DL in LO(LD); the scratch lines of factor_rows_at live in the four dead CG vectors (Ma .. search)
   VNL_HD void factor(bool with_loop = true) const {
-    const int nv = MI(nv), md = MI(max_depth);
-    // the scratch lines of factor_rows live in the four dead CG vectors (Ma .. search)
-    const int room = 4 * nv - 3 - 4 * VNL_FAC_LINES;
-    if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16 && VNL_FAC_LINES * 16 <= room) factor_rows<VNL_ROWSETS_1, 16>(with_loop);
-    else if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 36 && VNL_FAC_LINES * 36 <= room) factor_rows<VNL_ROWSETS_1, 36>(with_loop);
-    else if (nv <= VNL_ROWSETS_2 * VNL_LANES && md < 36 && VNL_FAC_LINES * 36 <= room && (MI(fac_nleaf) >> 8) < 16)
-      factor_rows<VNL_ROWSETS_2, 36, false, 16>(with_loop);  // (a second lane set with deeper rows takes the LDS route:
-                                                             // every instantiation costs registers for the whole kernel)
-    else factor_lds();
+    const int sc = (LO(Ma) + 3) & ~3;
+    switch (route(VNL_ROUTE_QM_FACTOR)) {
+      case VNL_ROUTE_ROWS16: factor_rows_at<VNL_ROWSETS_1, 16>(with_loop, LO(LD), LO(dinv), sc); break;
+      case VNL_ROUTE_ROWS36: factor_rows_at<VNL_ROWSETS_1, 36>(with_loop, LO(LD), LO(dinv), sc); break;
+      case VNL_ROUTE_ROWS36X2: factor_rows_at<VNL_ROWSETS_2, 36, 16>(with_loop, LO(LD), LO(dinv), sc); break;
+      default: factor_lds(LO(LD), LO(dinv), false);
+    }
   }
-  // solve (matrix in LD) x = s[rhs .. rhs+nv) in place without storing a factor; false if this model needs the
-  // general route (factor + invert_factor + solve_inplace)
-  VNL_HD bool factor_solve(int rhs) const {
-    const int nv = MI(nv), md = MI(max_depth);
-    const int room = 4 * nv - 3 - 4 * VNL_FAC_LINES;
-    if ((MI(fac_nleaf) & 0xff) == 0) return false;
-    if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16 && VNL_FAC_LINES * 16 <= room) factor_rows<VNL_ROWSETS_1, 16, true>(true, rhs);
-    else if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 36 && VNL_FAC_LINES * 36 <= room) factor_rows<VNL_ROWSETS_1, 36, true>(true, rhs);
-    else if (nv <= VNL_ROWSETS_2 * VNL_LANES && md < 36 && VNL_FAC_LINES * 36 <= room && (MI(fac_nleaf) >> 8) < 16)
-      factor_rows<VNL_ROWSETS_2, 36, true, 16>(true, rhs);
-    else return false;
-    return true;
-  }
-  // (LDb: where the factor sits -- LO(LD), or the copy of the second factor that euler() brings into the pool)
+  // (LDb: where the factor sits -- LO(LD), or the Newton Hessian's; the LDS form works on LO(LD) only, and build_dev_model
+  // admits a Newton model only where the inverse route is register-resident)
   VNL_HD void invert_factor(int LDb) const {
-    const int nv = MI(nv), md = MI(max_depth);
-    if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16) invert_rows<VNL_ROWSETS_1, 16>(LDb);
-    else if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 36) invert_rows<VNL_ROWSETS_1, 36>(LDb);
-    else if (nv <= VNL_ROWSETS_2 * VNL_LANES && md < 36 && (MI(fac_nleaf) >> 8) < 16) invert_rows<VNL_ROWSETS_2, 36, 16>(LDb);
-    else invert_factor_lds();  // (only ever reached with LDb == LO(LD): factor_pair_ok() excludes these models)
+    switch (route(VNL_ROUTE_QM_INVERSE)) {
+      case VNL_ROUTE_ROWS16: invert_rows<VNL_ROWSETS_1, 16>(LDb); break;
+      case VNL_ROUTE_ROWS36: invert_rows<VNL_ROWSETS_1, 36>(LDb); break;
+      case VNL_ROUTE_ROWS36X2: invert_rows<VNL_ROWSETS_2, 36, 16>(LDb); break;
+      default: invert_factor_lds();
+    }
   }
   VNL_HD void invert_factor() const { invert_factor(LO(LD)); }
 
@@ -2046,15 +1982,13 @@ struct EnvWaveT {
   // L'DL of the Hessian in place: the register-resident row elimination of qM's factor() with its scratch lines in the part of
   // the pool that the contact-wrench / dof prefix sums use (dead between constraint_force and the next jac_mul), else the LDS form
   VNL_HD void newton_factor(int Hb, int dinvb) const {
-    const int nv = MI(nv), md = MI(max_depth);
-    const int scb = (LO(P) + 3 * MI(nefc) + 3) & ~3, room = LO(smooth) - scb;
-    if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 16 && VNL_FAC_LINES * (16 + 4) <= room)
-      factor_rows_at<VNL_ROWSETS_1, 16, false, 16, true>(true, 0, Hb, dinvb, scb);
-    else if (nv <= VNL_ROWSETS_1 * VNL_LANES && md < 36 && VNL_FAC_LINES * (36 + 4) <= room)
-      factor_rows_at<VNL_ROWSETS_1, 36, false, 36, true>(true, 0, Hb, dinvb, scb);
-    else if (nv <= VNL_ROWSETS_2 * VNL_LANES && md < 36 && VNL_FAC_LINES * (36 + 4) <= room && (MI(fac_nleaf) >> 8) < 16)
-      factor_rows_at<VNL_ROWSETS_2, 36, false, 16, true>(true, 0, Hb, dinvb, scb);
-    else factor_lds(Hb, dinvb, true);
+    const int scb = (LO(P) + 3 * MI(nefc) + 3) & ~3;  // (vnl_lib.hip: choose_routes checks that the lines fit below LO(smooth))
+    switch (route(VNL_ROUTE_HESSIAN)) {
+      case VNL_ROUTE_ROWS16: factor_rows_at<VNL_ROWSETS_1, 16, 16, true>(true, Hb, dinvb, scb); break;
+      case VNL_ROUTE_ROWS36: factor_rows_at<VNL_ROWSETS_1, 36, 36, true>(true, Hb, dinvb, scb); break;
+      case VNL_ROUTE_ROWS36X2: factor_rows_at<VNL_ROWSETS_2, 36, 16, true>(true, Hb, dinvb, scb); break;
+      default: factor_lds(Hb, dinvb, true);
+    }
   }
   // out = qM v with qM's tree-sparse entries (symmetric: row i's own entries, then column i in the rows of i's descendants):
   // with search = -H^-1 grad the recurrence M s' = -grad + beta M s of the CG route does not hold
@@ -2353,11 +2287,9 @@ struct EnvWaveT {
       fresh().body_inertias(false);
       VNL_PROF(1);
       fresh().mass_matrix(m.dt);
-      if (!fresh().factor_solve(LO(tmp))) {
-        fresh().factor();
-        fresh().invert_factor();
-        fresh().solve_inplace(LO(tmp));
-      }
+      fresh().factor();
+      fresh().invert_factor();
+      fresh().solve_inplace(LO(tmp));
       VNL_PROF(27);
     }
     VNL_FOR(i, MI(nu)) {

@@ -312,6 +312,34 @@ static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm)
 // inverse weight of a contact's rows (constraint._instantiate_contact): at upload and, per env, in vnl_env_set_domain
 static double contact_invweight(double t, double mu, double impratio) { return (t + mu * mu * t) * 2 * mu * mu / impratio; }
 
+static VnlDims dims_of(const DevModel& d) {
+  return VnlDims{d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ncg, d.ncon, d.nlimit, d.nefc, d.nM, d.iterations, d.ls_iterations, d.eulerdamp,
+                 d.root_free, d.max_depth, d.jump_rounds, d.fac_steps, d.fac_route, d.solver_newton, d.blk_cfg, d.path_runs, d.nbody_out};
+}
+
+// The factorisation routes of a model (vnl_types.h: VNL_ROUTE_*), chosen here once; the kernels' dispatchers only read them.
+// The register-resident forms need their lane sets (nv <= 64, or <= 128 with the rows 64 .. of depth < 16: deep1), a bound on
+// the depth and room for VNL_FAC_LINES scratch lines of MAXD + 4 floats; the articulated-body pair needs eulerdamp, its V
+// store below cvel and its lines of 16 floats in the six dead vectors Mgrad .. tmp2.
+static int choose_routes(const DevModel& d, int deep1) {
+  const WsLayout L = vnl_make_layout(dims_of(d));  // (the layout does not depend on the routes)
+  const int nv = d.nv, md = d.max_depth, set1 = VNL_ROWSETS_1 * VNL_LANES, set2 = VNL_ROWSETS_2 * VNL_LANES;
+  auto rows = [&](int room) {  // room: floats for the scratch lines (-1: none needed, the inversion)
+    auto fits = [&](int maxd) { return room < 0 || VNL_FAC_LINES * (maxd + 4) <= room; };
+    if (nv <= set1 && md < 16 && fits(16)) return VNL_ROUTE_ROWS16;
+    if (nv <= set1 && md < 36 && fits(36)) return VNL_ROUTE_ROWS36;
+    if (nv <= set2 && md < 36 && deep1 < 16 && fits(36)) return VNL_ROUTE_ROWS36X2;
+    return VNL_ROUTE_LDS;
+  };
+  const int factor = rows(4 * nv - 3);  // qM: the lines in Ma .. search, from the first 16-byte boundary
+  const int inverse = rows(-1);
+  const int hessian = d.solver_newton ? rows(L.smooth - ((L.P + 3 * d.nefc + 3) & ~3)) : 0;  // the lines in the pool
+  const bool pair = d.eulerdamp && nv <= set2 && vnl_vstore(L.P) + 12 * nv <= vnl_cvel_at(L.P, L.smooth, d.nbody, nv) &&
+                    VNL_FAC_LINES * 16 + 3 <= 6 * nv;
+  return factor << VNL_ROUTE_QM_FACTOR | inverse << VNL_ROUTE_QM_INVERSE | hessian << VNL_ROUTE_HESSIAN |
+         (pair ? (nv <= set1 ? 1 : 2) : 0) << VNL_ROUTE_PAIR;
+}
+
 static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   DevModel& d = env->dm;
   vnl_model fused;
@@ -579,24 +607,12 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
     for (int j = nv - 1; j >= 0; j--)
       if (par[j] >= 0 && ftime[par[j]] <= ftime[j]) return fail(VNL_ERR_UNSUPPORTED, "factorisation schedule is not causal");
     d.fac_steps = (int)count.size();
-    {  // leaves of the dof tree, for the forward substitution of factor_rows<.., true>
-      std::vector<int> leaf_id(nv, -1);
-      int nleaf = 0;
-      for (int j = 0; j < nv; j++)
-        if (ndesc[j] == 0) leaf_id[j] = nleaf++;
-      d.fac_nleaf = nleaf <= VNL_FAC_LINES ? nleaf : 0;
-      int deep1 = 0;  // deepest row of the second lane set (rows 64 ..): bits 8.. of fac_nleaf
-      for (int j = 64; j < nv; j++) deep1 = depth[j] > deep1 ? depth[j] : deep1;
-      if (d.fac_nleaf)
-        for (int a = 0; a < nv; a++) {
-          int mask = 0;
-          for (int j = a; j <= a + ndesc[a]; j++)
-            if (leaf_id[j] >= 0) mask |= 1 << leaf_id[j];
-          fslot[a] |= (leaf_id[a + ndesc[a]] << 8) | (mask << 16);  // the last descendant is a leaf
-        }
-      d.fac_nleaf |= deep1 << 8;
-    }
     UPI(dof_ftime, ftime) UPI(dof_fslot, fslot)
+    {
+      int deep1 = 0;  // the deepest of the rows 64 .. (the second lane set)
+      for (int j = 64; j < nv; j++) deep1 = depth[j] > deep1 ? depth[j] : deep1;
+      d.fac_route = choose_routes(d, deep1);
+    }
     {  // guests of invert_aba: rows 64.. placed with lanes whose own row is shallow (deepest guests first), so that own + guest <= 36 entries
       d.fac_guest = nullptr;
       if (nv > 64 && nv <= 128) {
@@ -618,7 +634,7 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
       const int nst = d.fac_steps;
       std::vector<unsigned char> match((size_t)nv * (nst > 0 ? nst : 1), 0);
       for (int j = 0; j < nv; j++)
-        for (int a = par[j]; a >= 0; a = par[a]) match[(size_t)a * nst + ftime[j]] |= (unsigned char)(1u << (fslot[j] & 0xff));
+        for (int a = par[j]; a >= 0; a = par[a]) match[(size_t)a * nst + ftime[j]] |= (unsigned char)(1u << fslot[j]);
       const unsigned char* dp = nullptr;
       if ((rc = upload<unsigned char, unsigned char>(env, match, &dp)) != VNL_OK) return rc;
       d.fac_match = dp;
@@ -754,7 +770,7 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
     // The Newton solver's tree-sparse Hessian (EnvWaveT::newton_hessian) relies on every constraint row's Jacobian living on ONE
     // body's path to the root: a limit row on the single dof of its hinge (one limit row per dof: dof_limrow holds one), a
     // contact's rows on the path of the one dynamic body whose geom touches the plane.  Its factor is inverted in registers
-    // (EnvWaveT::invert_rows): the depth bounds of that form must hold.
+    // (EnvWaveT::invert_factor: the LDS form works on qM's place only).
     std::vector<int> nlim(nv, 0);
     for (int j = 0; j < nj; j++)
       if (I("jnt_limited")[j] && I("jnt_type")[j] == VNL_JNT_HINGE) {
@@ -766,17 +782,11 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
       const int b = I("cg_bodyid")[g];
       if (b < 0 || b >= nb) return fail(VNL_ERR_UNSUPPORTED, "Newton solver: a contact is not attached to one dynamic body");
     }
-    const int deep1 = d.fac_nleaf >> 8;
-    if (!(d.max_depth < 36 && (nv <= 64 || (nv <= 128 && deep1 < 16))))
+    if (((d.fac_route >> VNL_ROUTE_QM_INVERSE) & 0xf) == VNL_ROUTE_LDS)
       return fail(VNL_ERR_UNSUPPORTED, "Newton solver: dof tree too deep for the register-resident inversion of the "
                                        "Hessian's factor (max depth < 36; rows 64 .. of depth < 16; nv <= 128)");
   }
   return VNL_OK;
-}
-
-static VnlDims dims_of(const DevModel& d) {
-  return VnlDims{d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ncg, d.ncon, d.nlimit, d.nefc, d.nM, d.iterations, d.ls_iterations, d.eulerdamp,
-                 d.root_free, d.max_depth, d.jump_rounds, d.fac_steps, d.fac_nleaf, d.solver_newton, d.blk_cfg, d.path_runs, d.nbody_out};
 }
 
 static void layout(vnl_env* env) {
@@ -912,9 +922,10 @@ extern "C" int vnl_env_create(const vnl_model* hm, const vnl_envspec* es, int32_
     return fail(VNL_ERR_UNSUPPORTED, "model too large: per-env working set exceeds 64 KB of LDS");
   }
   {
-    int nb_ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, vnl_step_kernel<VnlSpecGeneric>, 64, env->lds_bytes) == hipSuccess)
-      env->blocks_per_cu = nb_;
+    int nb_ = 0;  // (of the step kernel this env runs)
+    hipError_t r = env->spec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, vnl_step_kernel<VnlSpecRodent>, 64, env->lds_bytes)
+                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, vnl_step_kernel<VnlSpecGeneric>, 64, env->lds_bytes);
+    if (r == hipSuccess) env->blocks_per_cu = nb_;
   }
   {
     KernelConsts host{env->dm, env->de, env->L};
@@ -936,6 +947,7 @@ extern "C" int vnl_env_dims(const vnl_env* env, vnl_dims* o) {
   o->workspace_floats_per_env = env->L.total;
   o->workgroups_per_cu = env->blocks_per_cu;
   o->nbody_dynamic = d.nbody, o->kernel_specialised = env->spec;
+  o->factor_route = d.fac_route;
   return VNL_OK;
 }
 

@@ -32,14 +32,26 @@ typedef VNL_REAL vreal;
 #define VNL_BLK_W 13 /* entries per block of EnvWave::blk_apply: with 13 the rodent's rows (113 blocks) AND columns (127) fit two trips of 64 lanes */
 #define VNL_FAC_LINES 6 /* pivots per factorisation step (scratch lines in the dead CG vectors) */
 
+/* Factorisation routes, chosen once per model by the host (vnl_lib.hip: choose_routes) and read by the dispatchers of
+ * EnvWaveT: one nibble each of DevModel::fac_route.  qM's factor (factor) and inverse (invert_factor), the Newton Hessian's
+ * factor (newton_factor; 0 for a CG model) take one of the four forms below; the pair nibble is 0, or the lane sets (1, 2)
+ * of the articulated-body form that makes both factors of a substep at once (factor_both / invert_both). */
+#define VNL_ROUTE_LDS 1      /* factor_lds / invert_factor_lds: the matrix stays in LDS, any tree */
+#define VNL_ROUTE_ROWS16 2   /* factor_rows_at / invert_rows with the rows in registers: nv <= 64, max_depth < 16 */
+#define VNL_ROUTE_ROWS36 3   /* nv <= 64, max_depth < 36 */
+#define VNL_ROUTE_ROWS36X2 4 /* two lane sets: nv <= 128, max_depth < 36, the rows 64 .. of depth < 16 */
+#define VNL_ROUTE_QM_FACTOR 0 /* bit offsets of the nibbles */
+#define VNL_ROUTE_QM_INVERSE 4
+#define VNL_ROUTE_HESSIAN 8
+#define VNL_ROUTE_PAIR 12
+
 struct DevModel {
   int nq, nv, nu, nbody, njnt, ncg, ncon, nlimit, nefc, nM;
   int iterations, ls_iterations, eulerdamp, root_free, max_depth, jump_rounds;
   int solver_newton; /* opt.solver == NEWTON (reference configs/env_config.yaml:16-21): 0 CG, 1 Newton with the tree-sparse
                         Hessian */
   int fac_steps; /* number of steps of the factorisation schedule */
-  int fac_nleaf; /* low byte: leaf dofs of the tree if <= VNL_FAC_LINES (factor_rows can then carry and solve a right-hand
-                    side), else 0; bits 8..: depth of the deepest of the rows 64 .. (second lane set) */
+  int fac_route; /* the factorisation routes of this model: VNL_ROUTE_* nibbles */
   int nbody_out; /* bodies of the model as given (rows of xpos / xquat): nbody counts the DYNAMIC bodies, welded ones folded into their parents */
   int path_runs; /* most runs of consecutive dofs / ancestor bodies any body's path has (<= 4): EnvWave::path_sum walks that many */
   int blk_cfg;   /* EnvWave::blk_apply: trips of the row form | trips of the column form << 4 | combine steps (row) << 8 | (column) << 12; 0 = no table */
@@ -70,7 +82,7 @@ struct DevModel {
   // dofs; tree-sparse qM layout (MuJoCo dof_Madr order: self, parent, grandparent, ...)
   const int *dof_body, *dof_Madr, *dof_depth, *dof_limrow;
   const int *M_anc, *M_row;          /* per entry: column dof / row dof */
-  const int *dof_ftime, *dof_fslot;  /* factorisation schedule: step in which row a is the pivot; scratch line | one leaf under a << 8 | mask of all leaves under a << 16 */
+  const int *dof_ftime, *dof_fslot;  /* factorisation schedule: step in which row a is the pivot; its scratch line in that step */
   const int* fac_guest;              /* [64] row 64.. that lane l inverts after its own row (EnvWave::invert_aba; -1: none); null if
                                         the model has no such rows or they cannot be placed (host depth <= 12, guest depth <= 24) */
   const unsigned* blk_tab;           /* [trips_row x 64 | trips_col x 64] block descriptors of blk_apply (vnl_lib.hip builds them); null if blk_cfg == 0 */
@@ -121,7 +133,6 @@ struct WsLayout {
   int con_r, con_t1;    /* 3 per contact / 3 per collidable geom */
   int tab_anc, tab_madr, tab_body, tab_jump, tab_lvl; /* 8/16-bit index tables staged in LDS */
   int act_list;         /* ncon bytes: contacts with D != 0, then their count (int) */
-  int pair_room;        /* elements from LD to the part of the pool that stays live across the factorisation (cvel): (kept for the layout's stability; the articulated-body factorisation needs 12 nv elements of the pool below cvel) */
   int newt_M, newt_H; /* Newton solver only: qM in the qLD layout (nM), the Hessian's inverted L'DL factor in that layout (nM)
                          followed by its reciprocal pivots (nv) */
   int total;
@@ -130,7 +141,7 @@ struct WsLayout {
 /* The integers the per-env LDS layout and the loop bounds of the kernels depend on. */
 struct VnlDims {
   int nq, nv, nu, nbody, njnt, ncg, ncon, nlimit, nefc, nM;
-  int iterations, ls_iterations, eulerdamp, root_free, max_depth, jump_rounds, fac_steps, fac_nleaf, solver_newton, blk_cfg, path_runs, nbody_out;
+  int iterations, ls_iterations, eulerdamp, root_free, max_depth, jump_rounds, fac_steps, fac_route, solver_newton, blk_cfg, path_runs, nbody_out;
 };
 
 /* The LDS layout as a function of the dims: evaluated by the host at env creation and, for a model the kernels are
@@ -162,7 +173,6 @@ constexpr WsLayout vnl_make_layout(const VnlDims& d) {
   if (d.eulerdamp) pool = vnl_imax(pool, d.nM + d.nv); /* euler() brings the second factor of the substep back into the pool */
   L.P = sec(pool);
   L.efc_D = L.P, L.Jaref = L.P + d.nefc, L.jv = L.P + 2 * d.nefc;
-  L.pair_room = (L.P + 16 * d.nbody) - L.LD; /* bias_forces keeps cvel at pool + 16 nbody until make_constraint has read it */
   L.smooth = sec(d.nv), L.qacc_smooth = sec(d.nv), L.qacc = sec(d.nv);
   L.Ma = sec(d.nv), L.grad = sec(d.nv), L.Mgrad = sec(d.nv), L.search = sec(d.nv);
   L.mv = sec(d.nv), L.qfrc_c = sec(d.nv), L.tmp = sec(d.nv), L.tmp2 = sec(d.nv);
@@ -182,6 +192,16 @@ constexpr WsLayout vnl_make_layout(const VnlDims& d) {
   return L;
 }
 
+/* The low end of the pool during a forward pass (EnvWaveT::vstore / cvel_at): factor_aba's store of the V vectors, 12 nv
+ * elements over crb from the pool's aligned start, and where bias_forces leaves cvel for make_constraint -- behind cacc / cfrc
+ * (pool + 16 nbody) and, where the pool has the room, behind the V store too (with the welded bodies folded away the body
+ * arrays are shorter than that store) */
+constexpr int vnl_vstore(int P) { return (P + 3) & ~3; }
+constexpr int vnl_cvel_at(int P, int smooth, int nbody, int nv) {
+  const int a = P + 16 * nbody, b = vnl_vstore(P) + 12 * nv;
+  return (b > a && b + 6 * nbody <= smooth) ? b : a;
+}
+
 /* Compile-time model of a kernel specialisation.  `fixed == false`: every dimension and LDS offset is read from the constant
  * block at run time (any model the library accepts).  `fixed == true`: they are the constants below -- loop bounds fold,
  * LDS offsets become instruction immediates, the scalar loads and address arithmetic of the generic kernel disappear; the
@@ -197,7 +217,8 @@ struct VnlSpecRodent {
   static constexpr bool fixed = true;
   static constexpr bool dom = false;
   // (53 dynamic bodies: 13 of the model's 66 are welded to their parents and folded into them, vnl_lib.hip: fuse_welded_bodies)
-  static constexpr VnlDims D{74, 73, 30, 53, 68, 32, 59, 67, 303, 1119, 6, 6, 1, 1, 35, 5, 36, 6 | (13 << 8), 0,
+  static constexpr VnlDims D{74, 73, 30, 53, 68, 32, 59, 67, 303, 1119, 6, 6, 1, 1, 35, 5, 36,
+                             VNL_ROUTE_ROWS36X2 | (VNL_ROUTE_ROWS36X2 << VNL_ROUTE_QM_INVERSE) | (2 << VNL_ROUTE_PAIR), 0,
                              2 | (2 << 4) | (2 << 8) | (3 << 12), 2, 66};
   static constexpr WsLayout L = vnl_make_layout(D);
 };
