@@ -188,6 +188,26 @@ typedef struct vnl_domain {
 } vnl_domain;
 int vnl_env_set_domain(vnl_env* env, const vnl_domain* domain, void* stream);
 
+/* Domain randomisation of the inertial fields: per-env body mass, principal moments and centre of mass over the bodies of
+ * the model AS GIVEN (nbody of vnl_dims: welded bodies included), float64 DEVICE pointers, row-major
+ *   body_mass [num_envs][nbody], body_inertia [num_envs][nbody][3] (in the frame of the compiled body_iquat, which is not
+ *   randomisable), body_ipos [num_envs][nbody][3];
+ * a null member leaves every env the compiled values; row 0 (the world body) is not read.  What the upload derives from the
+ * three fields is derived per env by the upload's own float64 code: the welded bodies folded into their parents (mass,
+ * centre of mass, full inertia of every dynamic body), the packed inertia and 1 / total mass; body / dof invweight0,
+ * meaninertia and body_subtreemass stay as compiled (MJX semantics).  An env's full inertia is the compiled one plus
+ * R(iquat) diag(body_inertia - compiled body_inertia) R(iquat)', so compiled values give bit-identical tables.
+ * Every value must be finite, masses and moments >= 0; after the fold every dynamic body that carries dofs must have
+ * mass > 0 and a positive diagonal of its inertia, and the total mass must be > 0 (else VNL_ERR_ARG with the field's name).
+ * Same contract as vnl_env_set_domain (waits for `stream`, copies and derives; null clears this part), and the two calls
+ * compose in either order: the part that is unset reads as the compiled values.  The model must carry body_inertia and
+ * body_iquat (VNL_ERR_BLOB otherwise).  vnl_env_scratch: "dom_mass" [num_envs][nd], "dom_ipos" [num_envs][3 nd],
+ * "dom_inertia6" [num_envs][6 nd] (xx yy zz xy xz yz), "dom_tminv" [num_envs][1], nd = nbody_dynamic. */
+typedef struct vnl_body_domain {
+  const double *body_mass, *body_inertia, *body_ipos;
+} vnl_body_domain;
+int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* domain, void* stream);
+
 /* Bisection hooks.  The per-env working set lives in LDS; with debug on, every reset/step
  * also copies it to a device dump [num_envs][row_stride]: enable = 1 at the end of the kernel,
  * enable = 2 (step only) as the LAST forward pass of the step leaves it, i.e. before the Euler

@@ -1,8 +1,9 @@
-"""Cost of domain randomisation (RodentTracking.with_domain): ms per control step of env.step at 4096 envs for the rodent
+"""Cost of domain randomisation (RodentTracking.with_domain, with_body_domain): ms per control step of env.step at 4096 envs for the rodent
 with CG 6 / 6 (the kernel specialised for the rodent) and Newton 6 / 6 (generic kernel, tree-sparse Hessian), each without a
 domain, with the identity domain (the compiled values: the randomised instantiation on the unrandomised numbers) and with a
-random domain (friction x U[0.4, 1.6], gain x U[0.7, 1.3], damping and armature x U[0.5, 2]); then the compiler's resource
-lines of the env kernels (VGPRs, SGPR spill, scratch, LDS).
+random domain (friction x U[0.4, 1.6], gain x U[0.7, 1.3], damping and armature x U[0.5, 2]), with the identity and a random
+body domain (mass x U[0.7, 1.3], moments x that x U[0.8, 1.25], ipos + U[-0.2, 0.2] |ipos|) and with both random parts; then
+the compiler's resource lines of the env kernels (VGPRs, SGPR spill, scratch, LDS).
 
     python tools/domain_bench.py [--envs 4096] [--steps 50] [--warmup 10] [--rounds 3]
 
@@ -49,6 +50,7 @@ def main() -> None:
     import numpy as np
     import torch
 
+    import body_domain_cases as BD
     import domain_cases as D
     import helpers as H
     from vnl_brax_imitation_amd.envs.rodent import RodentTracking
@@ -79,7 +81,10 @@ def main() -> None:
         m = copy.deepcopy(H.model())
         m.scalars.update(solver_newton=newton, iterations=6, ls_iterations=6)
         base = RodentTracking(H.reference_clip(), num_envs=B, device=dev, **dict(H.env_kwargs(), model=m))
-        envs = {"none": base, "identity": base.with_domain(D.identity(m, B)), "random": base.with_domain(D.random_domain(m, B, 0))}
+        envs = {"none": base, "identity": base.with_domain(D.identity(m, B)), "random": base.with_domain(D.random_domain(m, B, 0)),
+                "body_identity": base.with_body_domain(BD.identity(m, B)),
+                "body_random": base.with_body_domain(BD.random_body_domain(m, B, 0))}
+        envs["both_random"] = envs["random"].with_body_domain(BD.random_body_domain(m, B, 0))
         ms = {k: [] for k in envs}
         for _ in range(args.rounds):
             for k, env in envs.items():

@@ -138,6 +138,9 @@ class PPOHParams(C.Structure):  # include/vnl.h: vnl_ppo_hparams
 class Domain(C.Structure):  # include/vnl.h: vnl_domain (float64 device pointers, [num_envs][n]; null = the model's value)
     _fields_ = [(n, C.c_void_p) for n in ("cg_friction", "act_gain", "dof_damping", "dof_armature")]
 
+class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device pointers, [num_envs][nbody (x3)]; null = the model's value)
+    _fields_ = [(n, C.c_void_p) for n in ("body_mass", "body_inertia", "body_ipos")]
+
 
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
@@ -146,7 +149,7 @@ EXPORTS = (
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
-    "vnl_env_set_domain",
+    "vnl_env_set_domain", "vnl_env_set_body_domain",
 )
 _HIP_ONLY = ("vnl_policy_", "vnl_ppo_update_", "vnl_ppo_minibatch_")  # not in the test-only host simulation
 
@@ -172,6 +175,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.vnl_env_debug.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.vnl_env_scratch.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int32)]
     lib.vnl_env_set_domain.argtypes = [vp, C.POINTER(Domain), vp]
+    lib.vnl_env_set_body_domain.argtypes = [vp, C.POINTER(BodyDomain), vp]
     lib.vnl_rollout_post.argtypes = [C.POINTER(PostDesc), C.c_int32, vp]
     lib.vnl_ppo_head.argtypes = [C.POINTER(PPOHeadArgs), vp, vp]
     lib.vnl_gather_rows.argtypes = [C.POINTER(GatherDesc), vp]

@@ -304,10 +304,11 @@ struct EnvWaveT {
   VNL_HD vreal* gqfrc_act() const { return st.qfrc_actuator + (size_t)e * MI(nv); }
   // library-owned global scratch of this env: the second inverse factor of a substep (invert_aba) and its reciprocal pivots (factor_aba), nM + nv elements
   VNL_HD vreal* fac2() const { return ev.fac2 + (size_t)e * (MI(nM) + MI(nv)); }
-  // The model parameters a domain may randomise (vnl_env_set_domain), every read of them goes through here: the shared DevModel
-  // table, or in a randomised instantiation (SP::dom, csrc/vnl_domain.hip) this env's row of the per-env table (global memory,
-  // read at the same points; 960 B per env for the rodent)
-  enum { P_MU, P_INVW, P_GAIN, P_DAMP, P_ARM };
+  // The model parameters a domain may randomise, every read of them goes through here: the shared DevModel table, or in a
+  // randomised instantiation (SP::dom, csrc/vnl_domain.hip) this env's row of the per-env table (global memory, read at the
+  // same points).  par: the five tables of vnl_env_set_domain (960 B per env for the rodent); par_row / total_mass_inv
+  // below: the inertial tables of vnl_env_set_body_domain (P_MASS, P_IPOS, P_INERTIA6).
+  enum { P_MU, P_INVW, P_GAIN, P_DAMP, P_ARM, P_MASS, P_IPOS, P_INERTIA6 };
   template <int F>
   VNL_HD vreal par(int i) const {
     if constexpr (SP::dom) {
@@ -324,6 +325,25 @@ struct EnvWaveT {
       else if constexpr (F == P_DAMP) return m.dof_damping[i];
       else return m.dof_armature[i];
     }
+  }
+  // the inertial tables of the dynamic bodies (vnl_env_set_body_domain), read by body_inertias only: the start of the shared
+  // DevModel table, or of this env's row of the per-env one (10 nbody + 1 elements per env; the rodent: 2.1 KB)
+  template <int F>
+  VNL_HD const vreal* par_row() const {
+    if constexpr (SP::dom) {
+      const VNL_CAS DevDomain& d = kc->dom;
+      if constexpr (F == P_MASS) return d.body_mass + (size_t)e * MI(nbody);
+      else if constexpr (F == P_IPOS) return d.body_ipos + (size_t)e * 3 * MI(nbody);
+      else return d.body_inertia6 + (size_t)e * 6 * MI(nbody);
+    } else {
+      if constexpr (F == P_MASS) return m.body_mass;
+      else if constexpr (F == P_IPOS) return m.body_ipos;
+      else return m.body_inertia6;
+    }
+  }
+  VNL_HD vreal total_mass_inv() const {
+    if constexpr (SP::dom) return kc->dom.total_mass_inv[e];
+    else return m.total_mass_inv;
   }
   VNL_HD V3 gpos3(int b) const {
     const vreal* x = gxpos() + 3 * b;
@@ -529,11 +549,11 @@ struct EnvWaveT {
       }
       const int ob = m.body_out[b];
       M3 R = qmat(gquat4(ob));
-      vreal mass = m.body_mass[b];
-      V3 xip = gpos3(ob) + mmul(R, t3(m.body_ipos, b));
+      vreal mass = par_row<P_MASS>()[b];
+      V3 xip = gpos3(ob) + mmul(R, t3(par_row<P_IPOS>(), b));
       csum = csum + xip * mass;
       V3 r = xip - O;
-      const vreal* I6 = m.body_inertia6 + 6 * b;  // xx yy zz xy xz yz (body axes, about ipos)
+      const vreal* I6 = par_row<P_INERTIA6>() + 6 * b;  // xx yy zz xy xz yz (body axes, about ipos)
       vreal Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
       vreal T[9];
       for (int i = 0; i < 3; i++)
@@ -550,7 +570,7 @@ struct EnvWaveT {
     }
     if (with_com) {
       vreal cx = vnl_wave_sum(csum.x), cy = vnl_wave_sum(csum.y), cz = vnl_wave_sum(csum.z);
-      VNL_SERIAL { st3(LO(com), v3(cx * m.total_mass_inv, cy * m.total_mass_inv, cz * m.total_mass_inv)); }
+      VNL_SERIAL { st3(LO(com), v3(cx * total_mass_inv(), cy * total_mass_inv(), cz * total_mass_inv())); }
     }
     VNL_SYNC();
   }

@@ -1,5 +1,6 @@
-// Randomised instantiations of the env kernels (vnl_env_set_domain): the five randomisable model tables read per env from
-// KernelConsts::dom (EnvWaveT::par).  A translation unit of its own, so that the instantiations of vnl_lib.hip -- the
+// Randomised instantiations of the env kernels (vnl_env_set_domain, vnl_env_set_body_domain): the randomisable model tables --
+// five of the contact / actuator / dof parameters, four of the bodies' inertial parameters -- read per env from
+// KernelConsts::dom (EnvWaveT::par, par_row).  A translation unit of its own, so that the instantiations of vnl_lib.hip -- the
 // specialised rodent step kernel bench.py times among them -- are compiled exactly as without this feature (co-compiled
 // template instantiations perturb each other's register allocation).  The host simulation includes it from vnl_lib.hip.
 #include <hip/hip_runtime.h>

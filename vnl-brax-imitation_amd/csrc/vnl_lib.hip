@@ -115,8 +115,13 @@ struct vnl_env {
   // inverse weight is derived from, kept from the upload; the per-env tables [B][ncg | ncg | nu | nv | nv] once set
   std::vector<double> mu0, gain0, damp0, arm0, cg_t;
   double impratio = 1.0;
-  vreal* dom = nullptr;
+  vreal* dom = nullptr;  // the four-field tables, then the body tables [B][nd | 3 nd | 6 nd | 1] (nd dynamic bodies)
   int has_dom = 0;  // 1: vnl_env_reset / vnl_env_step launch the randomised instantiations (csrc/vnl_domain.hip)
+  int has_dom4 = 0, has_body = 0;  // which part was set (vnl_env_set_domain / vnl_env_set_body_domain); the other reads as compiled
+  // vnl_env_set_body_domain: the inertial fields of the model AS GIVEN and the fold of its welded bodies, kept from the upload
+  struct FuseMap* fmap = nullptr;
+  std::vector<double> mass0, ipos0, ifull0, inertia0, iquat0;  // (inertia0 / iquat0 empty: the blob does not carry them)
+  std::vector<int> dyn_dofnum;                                 // dofs of every dynamic body
   std::vector<void*> allocs;
   std::map<std::string, std::pair<int, int>> sections;  // name -> (offset, count)
 };
@@ -181,6 +186,67 @@ static void qmat_d(const double* q, double* R) {
 }
 static void mulv_d(const double* R, const double* v, double* o) {
   for (int r = 0; r < 3; r++) o[r] = R[3 * r] * v[0] + R[3 * r + 1] * v[1] + R[3 * r + 2] * v[2];
+}
+// The inertial part of the fold, shared by the upload and by vnl_env_set_body_domain (per env): mass / centre of mass / full
+// inertia of every dynamic body with what is welded to it, from the three arrays over the bodies as given.  Moments are
+// accumulated about the dynamic body's origin in its axes, then shifted back to the fused centre of mass.  A model without
+// welded bodies passes through unchanged.  float64 throughout; the callers cast to vreal last.
+static void fuse_inertial(const FuseMap& fmr, int nd, const double* mass, const double* ipos, const double* ifull,
+                          std::vector<double>* Mo, std::vector<double>* nipo, std::vector<double>* nIo) {
+  const FuseMap* fm = &fmr;
+  const int nb = fm->nb_out;
+  std::vector<double>&M = *Mo, &nip = *nipo, &nI = *nIo;
+  if (nd == nb) {
+    M.assign(mass, mass + nb), nip.assign(ipos, ipos + 3 * (size_t)nb), nI.assign(ifull, ifull + 9 * (size_t)nb);
+    return;
+  }
+  M.assign(nd, 0.0);
+  std::vector<double> mc(3 * (size_t)nd, 0.0), J(9 * (size_t)nd, 0.0);
+  for (int b = 0; b < nb; b++) {
+    const int dyn = fm->out_dyn[b];
+    double R[9], c[3], t[3];
+    qmat_d(&fm->out_quat[4 * (size_t)b], R), mulv_d(R, &ipos[3 * (size_t)b], t);
+    for (int k = 0; k < 3; k++) c[k] = fm->out_pos[3 * (size_t)b + k] + t[k];
+    const double m = mass[b], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+    M[dyn] += m;
+    for (int k = 0; k < 3; k++) mc[3 * (size_t)dyn + k] += m * c[k];
+    const double* I = &ifull[9 * (size_t)b];
+    for (int r = 0; r < 3; r++)
+      for (int q = 0; q < 3; q++) {
+        double v = 0;  // (R I R')(r, q)
+        for (int a = 0; a < 3; a++)
+          for (int e = 0; e < 3; e++) v += R[3 * r + a] * I[3 * a + e] * R[3 * q + e];
+        J[9 * (size_t)dyn + 3 * r + q] += v + m * ((r == q ? cc : 0.0) - c[r] * c[q]);
+      }
+  }
+  nip.assign(3 * (size_t)nd, 0.0), nI.assign(9 * (size_t)nd, 0.0);
+  for (int dyn = 0; dyn < nd; dyn++) {
+    double c[3] = {0, 0, 0};
+    if (M[dyn] > 0)
+      for (int k = 0; k < 3; k++) c[k] = mc[3 * (size_t)dyn + k] / M[dyn];
+    else
+      for (int k = 0; k < 3; k++) c[k] = ipos[3 * (size_t)fm->body_out[dyn] + k];
+    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+    for (int k = 0; k < 3; k++) nip[3 * (size_t)dyn + k] = c[k];
+    for (int r = 0; r < 3; r++)
+      for (int q = 0; q < 3; q++) nI[9 * (size_t)dyn + 3 * r + q] = J[9 * (size_t)dyn + 3 * r + q] - M[dyn] * ((r == q ? cc : 0.0) - c[r] * c[q]);
+  }
+}
+// body_inertia_full [nb][9] -> body_inertia6 [nb][6]: xx yy zz xy xz yz
+static std::vector<double> pack_inertia6(const std::vector<double>& f9) {
+  const size_t nb = f9.size() / 9;
+  std::vector<double> i6(6 * nb);
+  for (size_t b = 0; b < nb; b++) {
+    const double* s = &f9[9 * b];
+    double* o = &i6[6 * b];
+    o[0] = s[0], o[1] = s[4], o[2] = s[8], o[3] = s[1], o[4] = s[2], o[5] = s[5];
+  }
+  return i6;
+}
+static double total_mass_inv_of(const std::vector<double>& mass) {
+  double tm = 0;
+  for (double x : mass) tm += x;
+  return 1.0 / tm;
 }
 static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm) {
   const int nb = (int)in.scalar("nbody");
@@ -249,40 +315,8 @@ static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm)
     quat.insert(quat.end(), q, q + 4);
   }
   out->i["body_parentid"] = par, out->f["body_pos"] = pos, out->f["body_quat"] = quat;
-  // mass / centre of mass / inertia of every dynamic body with what is welded to it: moments about the body's origin, in its axes
-  std::vector<double> M(nd, 0.0), mc(3 * (size_t)nd, 0.0), J(9 * (size_t)nd, 0.0);
-  const auto& mass = in.f.at("body_mass");
-  const auto& ipos = in.f.at("body_ipos");
-  const auto& ifull = in.f.at("body_inertia_full");
-  for (int b = 0; b < nb; b++) {
-    const int dyn = fm->out_dyn[b];
-    double R[9], c[3], t[3];
-    qmat_d(&fm->out_quat[4 * (size_t)b], R), mulv_d(R, &ipos[3 * (size_t)b], t);
-    for (int k = 0; k < 3; k++) c[k] = fm->out_pos[3 * (size_t)b + k] + t[k];
-    const double m = mass[b], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    M[dyn] += m;
-    for (int k = 0; k < 3; k++) mc[3 * (size_t)dyn + k] += m * c[k];
-    const double* I = &ifull[9 * (size_t)b];
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 3; q++) {
-        double v = 0;  // (R I R')(r, q)
-        for (int a = 0; a < 3; a++)
-          for (int e = 0; e < 3; e++) v += R[3 * r + a] * I[3 * a + e] * R[3 * q + e];
-        J[9 * (size_t)dyn + 3 * r + q] += v + m * ((r == q ? cc : 0.0) - c[r] * c[q]);
-      }
-  }
-  std::vector<double> nip(3 * (size_t)nd, 0.0), nI(9 * (size_t)nd, 0.0);
-  for (int dyn = 0; dyn < nd; dyn++) {
-    double c[3] = {0, 0, 0};
-    if (M[dyn] > 0)
-      for (int k = 0; k < 3; k++) c[k] = mc[3 * (size_t)dyn + k] / M[dyn];
-    else
-      for (int k = 0; k < 3; k++) c[k] = ipos[3 * (size_t)fm->body_out[dyn] + k];
-    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    for (int k = 0; k < 3; k++) nip[3 * (size_t)dyn + k] = c[k];
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 3; q++) nI[9 * (size_t)dyn + 3 * r + q] = J[9 * (size_t)dyn + 3 * r + q] - M[dyn] * ((r == q ? cc : 0.0) - c[r] * c[q]);
-  }
+  std::vector<double> M, nip, nI;
+  fuse_inertial(*fm, nd, in.f.at("body_mass").data(), in.f.at("body_ipos").data(), in.f.at("body_inertia_full").data(), &M, &nip, &nI);
   out->f["body_mass"] = M, out->f["body_ipos"] = nip, out->f["body_inertia_full"] = nI;
   for (const char* k : {"jnt_bodyid", "dof_bodyid"}) {
     std::vector<int> v = in.i.at(k);
@@ -350,8 +384,18 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
     if (hm->f.find(k) == hm->f.end()) return fail(VNL_ERR_BLOB, "blob section %s missing", k);
   for (const char* k : {"jnt_bodyid", "dof_bodyid", "cg_bodyid", "body_jntadr", "body_rootid", "body_dofadr", "body_dofnum"})
     if (hm->i.find(k) == hm->i.end()) return fail(VNL_ERR_BLOB, "blob section %s missing", k);
+  {  // kept for vnl_env_set_body_domain: the inertial fields as given (the fold below replaces them in `fused`)
+    env->mass0 = hm->f.at("body_mass"), env->ipos0 = hm->f.at("body_ipos"), env->ifull0 = hm->f.at("body_inertia_full");
+    const size_t nbo = env->mass0.size();
+    if (env->ipos0.size() != 3 * nbo || env->ifull0.size() != 9 * nbo || (double)nbo != hm->scalar("nbody"))
+      return fail(VNL_ERR_BLOB, "blob section %s missing or of unexpected size", "body_ipos / body_inertia_full");
+    if (hm->has_f("body_inertia", 3 * nbo) && hm->has_f("body_iquat", 4 * nbo))
+      env->inertia0 = hm->f.at("body_inertia"), env->iquat0 = hm->f.at("body_iquat");
+  }
   if (fuse_welded_bodies(*hm, &fused, &fmap)) hm = &fused;
   d.nbody_out = fmap.nb_out;
+  env->fmap = new FuseMap(fmap);
+  env->dyn_dofnum = hm->i.at("body_dofnum");
   auto S = [&](const char* k) { return hm->scalar(k); };
   d.nq = (int)S("nq"), d.nv = (int)S("nv"), d.nu = (int)S("nu"), d.nbody = (int)S("nbody"), d.njnt = (int)S("njnt");
   d.ncg = (int)S("ncg"), d.ncon = (int)S("ncon"), d.nlimit = (int)S("nlimit"), d.nefc = (int)S("nefc");
@@ -416,9 +460,7 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
     double nn = sqrt(bb[0] * bb[0] + bb[1] * bb[1] + bb[2] * bb[2]);
     d.t1x = (vreal)(bb[0] / nn), d.t1y = (vreal)(bb[1] / nn), d.t1z = (vreal)(bb[2] / nn);
   }
-  double tm = 0;
-  for (double x : F("body_mass")) tm += x;
-  d.total_mass_inv = (vreal)(1.0 / tm);
+  d.total_mass_inv = (vreal)total_mass_inv_of(F("body_mass"));
 
   int rc;
 #define UPF(name, vec) if ((rc = upload<vreal, double>(env, vec, &d.name)) != VNL_OK) return rc;
@@ -505,16 +547,7 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
     }
   }
   UPF(body_pos, F("body_pos")) UPF(body_quat, F("body_quat")) UPF(body_ipos, F("body_ipos")) UPF(body_mass, F("body_mass"))
-  {
-    std::vector<double> i6(6 * (size_t)nb);
-    const auto& f9 = F("body_inertia_full");
-    for (int b = 0; b < nb; b++) {
-      const double* s = &f9[9 * (size_t)b];
-      double* o = &i6[6 * (size_t)b];
-      o[0] = s[0], o[1] = s[4], o[2] = s[8], o[3] = s[1], o[4] = s[2], o[5] = s[5];
-    }
-    UPF(body_inertia6, i6)
-  }
+  UPF(body_inertia6, pack_inertia6(F("body_inertia_full")))
   UPI(jnt_type, jt) UPI(jnt_qposadr, I("jnt_qposadr")) UPI(jnt_dofadr, I("jnt_dofadr")) UPI(jnt_body, I("jnt_bodyid"))
   UPF(jnt_pos, F("jnt_pos")) UPF(jnt_axis, F("jnt_axis")) UPF(jnt_stiffness, F("jnt_stiffness"))
   {
@@ -822,6 +855,7 @@ static bool same_dims(const VnlDims& a, const VnlDims& b) { return memcmp(&a, &b
 extern "C" void vnl_env_destroy(vnl_env* env) {
   if (!env) return;
   for (void* p : env->allocs) (void)hipFree(p);
+  delete env->fmap;
   delete env;
 }
 
@@ -954,12 +988,15 @@ extern "C" int vnl_env_dims(const vnl_env* env, vnl_dims* o) {
 extern "C" int vnl_env_scratch(const vnl_env* env, const char* name, float** dev_ptr, int32_t* count) {
   if (!env || !name || !dev_ptr || !count) return fail(VNL_ERR_ARG, "vnl_env_scratch: null argument");
   if (strncmp(name, "dom_", 4) == 0) {  // per-env parameter tables of a randomised env, [num_envs][count] (no debug needed)
-    if (!env->has_dom) return fail(VNL_ERR_ARG, "vnl_env_scratch: %s: the env has no domain (vnl_env_set_domain)", name);
+    if (!env->has_dom) return fail(VNL_ERR_ARG, "vnl_env_scratch: %s: the env has no domain (vnl_env_set_domain / vnl_env_set_body_domain)", name);
     const DevModel& d = env->dm;
     const size_t B = (size_t)env->B;
+    const size_t n4 = B * (2 * d.ncg + d.nu + 2 * d.nv), nd = (size_t)d.nbody;  // (the layout of domain_tables below)
     const struct { const char* k; size_t off; int n; } tabs[] = {
         {"dom_mu", 0, d.ncg}, {"dom_invw", B * d.ncg, d.ncg}, {"dom_gain", 2 * B * d.ncg, d.nu},
-        {"dom_damp", B * (2 * d.ncg + d.nu), d.nv}, {"dom_arm", B * (2 * d.ncg + d.nu + d.nv), d.nv}};
+        {"dom_damp", B * (2 * d.ncg + d.nu), d.nv}, {"dom_arm", B * (2 * d.ncg + d.nu + d.nv), d.nv},
+        {"dom_mass", n4, d.nbody}, {"dom_ipos", n4 + B * nd, 3 * d.nbody}, {"dom_inertia6", n4 + 4 * B * nd, 6 * d.nbody},
+        {"dom_tminv", n4 + 10 * B * nd, 1}};
     for (const auto& t : tabs)
       if (strcmp(name, t.k) == 0) {
         *dev_ptr = (float*)(env->dom + t.off);
@@ -1094,11 +1131,124 @@ extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* 
   return VNL_OK;
 }
 
-// Domain randomisation: per-env friction, actuator gain, damping and armature (brax / MJX semantics: the raw fields are
-// replaced, the derived constants -- dof / body invweight0, meaninertia, scale -- stay as compiled), except the contact rows'
-// mu and inverse weight, which the upload derives from friction and which are derived here per env by the same float64
-// expression: a domain equal to the compiled values gives bit-identical tables.  Synchronous: waits for `stream`, reads the
-// inputs to the host, validates, derives, writes the library-owned tables.
+// Domain randomisation (brax / MJX semantics: raw fields are replaced, the derived constants -- dof / body invweight0,
+// meaninertia, scale -- stay as compiled), in two parts that compose: vnl_env_set_domain (friction, actuator gain, damping,
+// armature) and vnl_env_set_body_domain (body mass, principal moments, centre of mass).  What the upload derives from these
+// fields -- the contact rows' mu and inverse weight; the fold of the welded bodies, the packed inertia, 1 / total mass -- is
+// derived here per env by the upload's own float64 code, so values equal to the compiled ones give bit-identical tables.  One
+// set of randomised kernels reads all nine tables: the part that was not set holds the compiled values in every env.
+// Synchronous: the calls wait for `stream`, read the inputs to the host, validate, derive, write the library-owned tables.
+
+// the four-field tables of `v` (per field [B][n] float64): [B][ncg] mu | [B][ncg] invweight | [B][nu] gain | [B][nv] damping |
+// [B][nv] armature, cast to vreal as the upload does
+static std::vector<vreal> four_field_tables(const vnl_env* env, const std::vector<double> v[4]) {
+  const DevModel& d = env->dm;
+  std::vector<vreal> tab;
+  tab.reserve((size_t)env->B * (2 * d.ncg + d.nu + 2 * d.nv));
+  for (double x : v[0]) tab.push_back((vreal)x);
+  for (size_t k = 0; k < v[0].size(); k++) tab.push_back((vreal)contact_invweight(env->cg_t[k % d.ncg], v[0][k], env->impratio));
+  for (int f = 1; f < 4; f++)
+    for (double x : v[f]) tab.push_back((vreal)x);
+  return tab;
+}
+static std::vector<vreal> four_field_compiled(const vnl_env* env) {
+  const std::vector<double>* model[4] = {&env->mu0, &env->gain0, &env->damp0, &env->arm0};
+  std::vector<double> v[4];
+  for (int f = 0; f < 4; f++)
+    for (int e = 0; e < env->B; e++) v[f].insert(v[f].end(), model[f]->begin(), model[f]->end());
+  return four_field_tables(env, v);
+}
+
+// One env's row of the body tables from its three raw arrays over the bodies as given (null: the compiled array): the
+// upload's fold and packing.  out: [nd] mass | [3 nd] ipos | [6 nd] inertia6 | 1 / total mass, float64.  Returns the name of
+// the field at fault (and `why`), or null; with a null `why` nothing is validated (the compiled values: what the upload
+// accepted is what an unset part reads).
+static const char* body_row(const vnl_env* env, const double* mass, const double* inertia, const double* ipos, std::vector<double>* out,
+                            char* why, size_t nwhy) {
+  const int nb = env->fmap->nb_out, nd = env->dm.nbody;
+  std::vector<double> full;
+  if (inertia) {  // compiled full inertia + R diag(moments - compiled moments) R': exactly the compiled one where they are equal
+    full = env->ifull0;
+    for (int b = 1; b < nb; b++) {
+      double dl[3], R[9];
+      for (int k = 0; k < 3; k++) dl[k] = inertia[3 * (size_t)b + k] - env->inertia0[3 * (size_t)b + k];
+      if (dl[0] == 0 && dl[1] == 0 && dl[2] == 0) continue;
+      qmat_d(&env->iquat0[4 * (size_t)b], R);
+      for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 3; q++) {
+          double v = 0;
+          for (int a = 0; a < 3; a++) v += R[3 * r + a] * dl[a] * R[3 * q + a];
+          full[9 * (size_t)b + 3 * r + q] += v;
+        }
+    }
+  }
+  std::vector<double> M, nip, nI;
+  fuse_inertial(*env->fmap, nd, mass ? mass : env->mass0.data(), ipos ? ipos : env->ipos0.data(),
+                inertia ? full.data() : env->ifull0.data(), &M, &nip, &nI);
+  double tm = 0;
+  for (int b = 0; b < nd; b++) {
+    tm += M[b];
+    if (!why || b == 0 || env->dyn_dofnum[b] <= 0) continue;
+    if (!(M[b] > 0)) {
+      snprintf(why, nwhy, "dynamic body %d (body %d as given, with what is welded to it) carries dofs and has mass %g", b, env->fmap->body_out[b], M[b]);
+      return "body_mass";
+    }
+    for (int k = 0; k < 3; k++)
+      if (!(nI[9 * (size_t)b + 4 * k] > 0)) {
+        snprintf(why, nwhy, "dynamic body %d (body %d as given) carries dofs and has inertia diagonal %g", b, env->fmap->body_out[b], nI[9 * (size_t)b + 4 * k]);
+        return "body_inertia";
+      }
+  }
+  if (why && !(tm > 0)) {
+    snprintf(why, nwhy, "total mass %g", tm);
+    return "body_mass";
+  }
+  const std::vector<double> i6 = pack_inertia6(nI);
+  out->clear();
+  out->insert(out->end(), M.begin(), M.end()), out->insert(out->end(), nip.begin(), nip.end());
+  out->insert(out->end(), i6.begin(), i6.end()), out->push_back(total_mass_inv_of(M));
+  return nullptr;
+}
+// rows [B][10 nd + 1] -> the body tables [B][nd] | [B][3 nd] | [B][6 nd] | [B], cast to vreal last
+static std::vector<vreal> body_tables(const vnl_env* env, const std::vector<std::vector<double>>& rows) {
+  const size_t B = (size_t)env->B, nd = (size_t)env->dm.nbody;
+  std::vector<vreal> tab(B * (10 * nd + 1));
+  const size_t off[4] = {0, B * nd, 4 * B * nd, 10 * B * nd}, w[4] = {nd, 3 * nd, 6 * nd, 1}, at[4] = {0, nd, 4 * nd, 10 * nd};
+  for (size_t e = 0; e < B; e++) {
+    const std::vector<double>& r = rows[rows.size() == 1 ? 0 : e];
+    for (int t = 0; t < 4; t++)
+      for (size_t k = 0; k < w[t]; k++) tab[off[t] + e * w[t] + k] = (vreal)r[at[t] + k];
+  }
+  return tab;
+}
+static std::vector<vreal> body_compiled(const vnl_env* env) {
+  std::vector<std::vector<double>> rows(1);
+  (void)body_row(env, nullptr, nullptr, nullptr, &rows[0], nullptr, 0);
+  return body_tables(env, rows);
+}
+
+// allocates the tables once, both parts holding the compiled values, and points KernelConsts::dom at them
+static int domain_tables(vnl_env* env) {
+  if (env->dom) return VNL_OK;
+  const DevModel& d = env->dm;
+  const size_t B = (size_t)env->B, n4 = B * (2 * d.ncg + d.nu + 2 * d.nv), nd = (size_t)d.nbody;
+  std::vector<vreal> tab = four_field_compiled(env);
+  const std::vector<vreal> body = body_compiled(env);
+  tab.insert(tab.end(), body.begin(), body.end());
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, tab.size() * sizeof(vreal)));
+  env->allocs.push_back(p);
+  HIPCHK(hipMemcpy(p, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
+  env->dom = (vreal*)p;
+  DevDomain dd;
+  dd.cg_mu = env->dom, dd.cg_invweight = env->dom + B * d.ncg, dd.act_gain = env->dom + 2 * B * d.ncg;
+  dd.dof_damping = dd.act_gain + B * d.nu, dd.dof_armature = dd.dof_damping + B * d.nv;
+  dd.body_mass = env->dom + n4, dd.body_ipos = dd.body_mass + B * nd, dd.body_inertia6 = dd.body_mass + 4 * B * nd;
+  dd.total_mass_inv = dd.body_mass + 10 * B * nd;
+  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, dom), &dd, sizeof(DevDomain), hipMemcpyHostToDevice));
+  return VNL_OK;
+}
+
 extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* stream) {
   if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_domain: null env");
   DeviceGuard guard(env->device);
@@ -1108,12 +1258,16 @@ extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* str
 #else
   (void)stream;
 #endif
-  if (!dom) {
-    env->has_dom = 0;
-    return VNL_OK;
-  }
   const DevModel& d = env->dm;
   const size_t B = (size_t)env->B;
+  if (!dom) {
+    if (env->dom) {  // (the tables outlive the clear -- the other part may be set, now or later: back to the compiled values)
+      const std::vector<vreal> tab = four_field_compiled(env);
+      if (!tab.empty()) HIPCHK(hipMemcpy(env->dom, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
+    }
+    env->has_dom4 = 0, env->has_dom = env->has_body;
+    return VNL_OK;
+  }
   struct Field {
     const char* name;
     const double* src;
@@ -1144,25 +1298,76 @@ extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* str
       }
     }
   }
-  // [B][ncg] mu | [B][ncg] invweight | [B][nu] gain | [B][nv] damping | [B][nv] armature, cast to vreal as the upload does
-  std::vector<vreal> tab;
-  tab.reserve(B * (2 * d.ncg + d.nu + 2 * d.nv));
-  for (double x : v[0]) tab.push_back((vreal)x);
-  for (size_t k = 0; k < v[0].size(); k++) tab.push_back((vreal)contact_invweight(env->cg_t[k % d.ncg], v[0][k], env->impratio));
-  for (int f = 1; f < 4; f++)
-    for (double x : v[f]) tab.push_back((vreal)x);
-  if (!env->dom) {
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, (tab.empty() ? 1 : tab.size()) * sizeof(vreal)));
-    env->allocs.push_back(p);
-    env->dom = (vreal*)p;
-  }
+  const std::vector<vreal> tab = four_field_tables(env, v);
+  int rc = domain_tables(env);
+  if (rc != VNL_OK) return rc;
   if (!tab.empty()) HIPCHK(hipMemcpy(env->dom, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
-  DevDomain dd;
-  dd.cg_mu = env->dom, dd.cg_invweight = env->dom + B * d.ncg, dd.act_gain = env->dom + 2 * B * d.ncg;
-  dd.dof_damping = dd.act_gain + B * d.nu, dd.dof_armature = dd.dof_damping + B * d.nv;
-  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, dom), &dd, sizeof(DevDomain), hipMemcpyHostToDevice));
-  env->has_dom = 1;
+  env->has_dom4 = 1, env->has_dom = 1;
+  return VNL_OK;
+}
+
+extern "C" int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* bd, void* stream) {
+  if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_body_domain: null env");
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+#ifndef VNL_FORKJOIN_DEFINED
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+#else
+  (void)stream;
+#endif
+  const DevModel& d = env->dm;
+  const size_t B = (size_t)env->B, nb = (size_t)d.nbody_out, n4 = B * (2 * d.ncg + d.nu + 2 * d.nv);
+  if (!bd) {
+    if (env->dom) {
+      const std::vector<vreal> tab = body_compiled(env);
+      HIPCHK(hipMemcpy(env->dom + n4, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
+    }
+    env->has_body = 0, env->has_dom = env->has_dom4;
+    return VNL_OK;
+  }
+  if (bd->body_inertia && env->inertia0.empty())
+    return fail(VNL_ERR_BLOB, "vnl_env_set_body_domain: body_inertia needs the model's body_inertia and body_iquat sections");
+  struct Field {
+    const char* name;
+    const double* src;
+    const std::vector<double>& model;
+    size_t w;
+    bool nonneg;
+  } fields[] = {{"body_mass", bd->body_mass, env->mass0, 1, true}, {"body_inertia", bd->body_inertia, env->inertia0, 3, true},
+                {"body_ipos", bd->body_ipos, env->ipos0, 3, false}};
+  std::vector<double> v[3];
+  for (int f = 0; f < 3; f++) {
+    const Field& F = fields[f];
+    if (!F.src) continue;
+    const size_t n = nb * F.w;
+    v[f].resize(B * n);
+    HIPCHK(hipMemcpy(v[f].data(), F.src, v[f].size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < B; e++) std::copy(F.model.begin(), F.model.begin() + F.w, v[f].begin() + e * n);  // row 0 is not read
+    for (size_t k = 0; k < v[f].size(); k++) {
+      const double x = v[f][k];
+      if (!(std::isfinite(x) && (!F.nonneg || x >= 0))) {
+        char where[96];
+        snprintf(where, sizeof(where), "env %zu, index %zu (%g)", k / n, k % n, x);
+        return fail(VNL_ERR_ARG, F.nonneg ? "vnl_env_set_body_domain: %s must be finite and >= 0: %s"
+                                          : "vnl_env_set_body_domain: %s must be finite: %s", F.name, where);
+      }
+    }
+  }
+  std::vector<std::vector<double>> rows(B);
+  for (size_t e = 0; e < B; e++) {
+    char why[160], where[200];
+    const char* bad = body_row(env, v[0].empty() ? nullptr : &v[0][e * nb], v[1].empty() ? nullptr : &v[1][e * 3 * nb],
+                               v[2].empty() ? nullptr : &v[2][e * 3 * nb], &rows[e], why, sizeof(why));
+    if (bad) {
+      snprintf(where, sizeof(where), "env %zu: %s", e, why);
+      return fail(VNL_ERR_ARG, "vnl_env_set_body_domain: %s: %s", bad, where);
+    }
+  }
+  const std::vector<vreal> tab = body_tables(env, rows);
+  int rc = domain_tables(env);
+  if (rc != VNL_OK) return rc;
+  HIPCHK(hipMemcpy(env->dom + n4, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
+  env->has_body = 1, env->has_dom = 1;
   return VNL_OK;
 }
 

@@ -222,8 +222,10 @@ struct VnlSpecRodent {
                              2 | (2 << 4) | (2 << 8) | (3 << 12), 2, 66};
   static constexpr WsLayout L = vnl_make_layout(D);
 };
-/* Domain randomisation (vnl_env_set_domain): the same kernel as BASE, with the five randomisable model tables read per env
- * from KernelConsts::dom instead of the shared DevModel tables (EnvWaveT::par).  Instantiated in csrc/vnl_domain.hip only. */
+/* Domain randomisation (vnl_env_set_domain, vnl_env_set_body_domain): the same kernel as BASE, with the randomisable model
+ * tables read per env from KernelConsts::dom instead of the shared DevModel tables -- five of the contact / actuator / dof
+ * parameters (EnvWaveT::par), four of the bodies' inertial parameters (EnvWaveT::par_row, total_mass_inv).  Instantiated in
+ * csrc/vnl_domain.hip only. */
 template <class BASE>
 struct VnlSpecDom : BASE {
   static constexpr bool dom = true;
@@ -234,6 +236,9 @@ struct DevDomain {
   const vreal *cg_mu, *cg_invweight; /* [B][ncg]: friction and the contact rows' inverse weight derived from it */
   const vreal *act_gain;             /* [B][nu] */
   const vreal *dof_damping, *dof_armature; /* [B][nv] */
+  /* vnl_env_set_body_domain, over the DYNAMIC bodies (welded ones folded per env): what EnvWaveT::body_inertias reads */
+  const vreal *body_mass, *body_ipos, *body_inertia6; /* [B][nbody], [B][3 nbody], [B][6 nbody] */
+  const vreal *total_mass_inv;                        /* [B] */
 };
 
 /* Everything the env kernels read that does not change between launches, in one device buffer.  The kernels read

@@ -36,6 +36,9 @@ _METRICS = ("rcom", "rvel", "rtrunk", "rquat", "ract", "rapp", "termination_erro
 # whether the bound itself is allowed; None: any finite value)
 DOMAIN_FIELDS = {"cg_friction": ("ngeom_collide", 0.0, False), "act_gain": ("nu", None, False),
                  "dof_damping": ("nv", 0.0, True), "dof_armature": ("nv", 0.0, True)}
+# the inertial fields a body domain may set per env, over the bodies of the model as given (include/vnl.h: vnl_body_domain)
+# -> (trailing shape after (num_envs, nbody), smallest allowed value; None: any finite value)
+BODY_DOMAIN_FIELDS = {"body_mass": ((), 0.0), "body_inertia": ((3,), 0.0), "body_ipos": ((3,), None)}
 
 
 def packaged_model_path(name: str = "rodent", scale_factor: Optional[float] = 0.9) -> str:
@@ -199,6 +202,25 @@ class RodentTracking(Env):
         return new
 
     _domain = None  # {field: (num_envs, n) float64 tensor} of a randomised env (with_domain), else None
+    _body_domain = None  # {field: (num_envs, nbody[, 3]) float64 tensor} of a body-randomised env (with_body_domain), else None
+
+    def _with_domains(self, tables, body_tables) -> "RodentTracking":
+        """A new env of this configuration and num_envs with the given parts of a domain (already validated; None: unset)."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self._config_attrs)
+        new._build(self._build_args[0], self.num_envs, *self._build_args[1:])
+        if tables is not None:
+            desc = _lib.Domain(**{k: C.c_void_p(t.data_ptr()) for k, t in tables.items()})
+            _lib.check(new._L, new._L.vnl_env_set_domain(new._env_h, C.byref(desc), new._stream()))  # (copies: synchronous)
+            new._domain = dict(tables)
+        if body_tables is not None:
+            desc = _lib.BodyDomain(**{k: C.c_void_p(t.data_ptr()) for k, t in body_tables.items()})
+            rc = new._L.vnl_env_set_body_domain(new._env_h, C.byref(desc), new._stream())
+            if rc == -1:  # VNL_ERR_ARG: what only the per-env fold can tell (a jointed body without mass, ...)
+                raise ValueError(new._L.vnl_last_error().decode())
+            _lib.check(new._L, rc)
+            new._body_domain = dict(body_tables)
+        return new
 
     def with_domain(self, domain: Mapping[str, Any]) -> "RodentTracking":
         """A NEW env of the same model, clip, parameters and num_envs whose envs each run with their own values of the raw
@@ -210,9 +232,9 @@ class RodentTracking(Env):
 
         A field left out keeps the model's value.  Derived constants (invweight0, meaninertia) stay as compiled; the contact
         rows' inverse weight follows friction.  Values are fixed for the env's lifetime (auto-reset keeps them).  Neither this
-        env nor its CompiledModel is changed.  `with_num_envs` of the result carries NO domain: an eval env is randomised by a
-        call of its own.  Raises ValueError on an unknown field, a wrong shape or a bad value (non-finite, friction <= 0,
-        damping or armature < 0)."""
+        env nor its CompiledModel is changed.  A body domain of this env (with_body_domain) is carried over.  `with_num_envs`
+        of the result carries NO domain: an eval env is randomised by a call of its own.  Raises ValueError on an unknown
+        field, a wrong shape or a bad value (non-finite, friction <= 0, damping or armature < 0)."""
         d = self.dims
         tables = {}
         for k, v in dict(domain).items():
@@ -228,22 +250,50 @@ class RodentTracking(Env):
             if lo is not None and not bool(((t >= lo) if closed else (t > lo)).all()):
                 raise ValueError(f"domain field {k!r} must be {'>=' if closed else '>'} {lo}")
             tables[k] = t.to(self.device).contiguous()
-        new = object.__new__(type(self))
-        new.__dict__.update(self._config_attrs)
-        new._build(self._build_args[0], self.num_envs, *self._build_args[1:])
-        desc = _lib.Domain(**{k: C.c_void_p(t.data_ptr()) for k, t in tables.items()})
-        _lib.check(new._L, new._L.vnl_env_set_domain(new._env_h, C.byref(desc), new._stream()))  # (copies: synchronous)
-        new._domain = tables
-        return new
+        return self._with_domains(tables, self._body_domain)
+
+    def with_body_domain(self, bodies: Mapping[str, Any]) -> "RodentTracking":
+        """A NEW env of the same model, clip, parameters and num_envs whose envs each run with their own inertial fields,
+        over the bodies of the model as given (MJX semantics; include/vnl.h: vnl_env_set_body_domain):
+
+          body_mass     (num_envs, nbody)
+          body_inertia  (num_envs, nbody, 3)  principal moments in the frame of the compiled body_iquat
+          body_ipos     (num_envs, nbody, 3)  centre of mass in the body frame
+
+        A field left out keeps the model's values; row 0 (the world body) is not read.  The library folds welded bodies into
+        their parents per env and derives 1 / total mass per env; invweight0, meaninertia and body_subtreemass stay as
+        compiled.  A four-field domain of this env (with_domain) is carried over, and `with_domain` of the result carries the
+        body domain; `with_num_envs` carries neither.  Neither this env nor its CompiledModel is changed.  Raises ValueError
+        on an unknown field, a wrong shape, a non-finite value, a negative mass or moment, a body with dofs left without
+        mass or inertia once welded bodies are folded in, or a total mass of zero."""
+        nbody = int(self.dims.nbody)
+        tables = {}
+        for k, v in dict(bodies).items():
+            if k not in BODY_DOMAIN_FIELDS:
+                raise ValueError(f"unknown body domain field {k!r}: expected some of {sorted(BODY_DOMAIN_FIELDS)}")
+            tail, lo = BODY_DOMAIN_FIELDS[k]
+            t = torch.as_tensor(v).detach().to(dtype=torch.float64)
+            shape = (self.num_envs, nbody) + tail
+            if tuple(t.shape) != shape:
+                raise ValueError(f"body domain field {k!r} must have shape {shape}, got {tuple(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"body domain field {k!r} has non-finite values")
+            if lo is not None and not bool((t[:, 1:] >= lo).all()):
+                raise ValueError(f"body domain field {k!r} must be >= {lo}")
+            tables[k] = t.to(self.device).contiguous()
+        return self._with_domains(self._domain, tables)
 
     @property
     def domain(self) -> Optional[Dict[str, torch.Tensor]]:
-        """The per-env field values this env was built with (with_domain), or None."""
-        return None if self._domain is None else dict(self._domain)
+        """The per-env field values this env was built with (with_domain and with_body_domain, both parts), or None."""
+        if self._domain is None and self._body_domain is None:
+            return None
+        return dict(self._domain or {}, **(self._body_domain or {}))
 
     def domain_table(self, name: str) -> torch.Tensor:
         """(num_envs, n) copy of one of the library's per-env tables of a randomised env (vnl_env_scratch "dom_mu",
-        "dom_invw", "dom_gain", "dom_damp", "dom_arm"): what the kernels read."""
+        "dom_invw", "dom_gain", "dom_damp", "dom_arm"; the body tables over the dynamic bodies "dom_mass", "dom_ipos",
+        "dom_inertia6", "dom_tminv"): what the kernels read."""
         ptr, cnt = C.c_void_p(), C.c_int32()
         _lib.check(self._L, self._L.vnl_env_scratch(self._env_h, name.encode(), C.byref(ptr), C.byref(cnt)))
         total = self.num_envs * cnt.value

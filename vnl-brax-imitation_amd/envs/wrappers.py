@@ -148,10 +148,18 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
     """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
 
     `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
-    num_envs and rng): its result goes to `env.with_domain`, a NEW env with per-env model parameters (RodentTracking.
-    with_domain: cg_friction, act_gain, dof_damping, dof_armature).  The caller's env is left as it is."""
+    num_envs and rng): its result goes to `env.with_domain` (cg_friction, act_gain, dof_damping, dof_armature) and, for the
+    keys body_mass, body_inertia, body_ipos, to `env.with_body_domain`: a NEW env with per-env model parameters.  An unknown
+    key raises.  The caller's env is left as it is."""
     if randomization_fn is not None:
         if not hasattr(env, "with_domain"):
             raise ValueError(f"{type(env).__name__} has no with_domain: domain randomisation needs a tracking env of this library")
-        env = env.with_domain(randomization_fn(env.sys))
+        from .rodent import BODY_DOMAIN_FIELDS
+
+        domain = dict(randomization_fn(env.sys))
+        bodies = {k: domain.pop(k) for k in list(domain) if k in BODY_DOMAIN_FIELDS}
+        if domain or not bodies:  # (an unknown key is with_domain's to refuse)
+            env = env.with_domain(domain)
+        if bodies:
+            env = env.with_body_domain(bodies)
     return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset)
