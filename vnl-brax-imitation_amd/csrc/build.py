@@ -17,6 +17,8 @@ OUT = os.path.join(HERE, "libvnl.so")
 #   knobs  -DVNL_STAGE_KNOBS  stage-repeat knob VNL_DBG_REPEAT + LDS padding knob (tools/stage_cost.py, tools/pmc_stage.sh)
 #   noblk  -DVNL_NO_BLK: the products with the factor / its inverse one lane per row / column (regression build for the
 #          balanced blocked form, EnvWave::blk_apply: same sums in another order)
+#   tail   -DVNL_SOLVER_TAIL: the solver's last permitted iteration computes its gradient / M^-1 grad / search update
+#          although nothing reads them (regression build for the skipped tail of EnvWave::solve: the same bits on every output)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -28,6 +30,7 @@ VARIANTS = {
     "knobs": ("libvnl_knobs.so", ["-DVNL_STAGE_KNOBS", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "spill": ("libvnl_spill.so", ["-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(4,4)))"]),
     "noblk": ("libvnl_noblk.so", ["-DVNL_NO_BLK", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "tail": ("libvnl_tail.so", ["-DVNL_SOLVER_TAIL", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

@@ -2118,6 +2118,19 @@ struct EnvWaveT {
       for_live_rows([&](int r) { s[LO(Jaref) + r] += alpha * s[LO(jv) + r]; });
       VNL_SYNC();
       VNL_PROF(20);
+      // ---- the last pass the iteration count allows: the loop cannot run again, and all that is read after it is qacc
+      // (warm start, euler) and qfrc_c (euler), so only constraint_force() is still wanted -- not its cost, the Gauss term,
+      // the new gradient, M^-1 grad (on the Newton route a whole Hessian assembly + factorisation + inversion) or the new
+      // search direction.  With the debug image on (trace set: wave-uniform) the full pass runs, since the image shows
+      // grad / Mgrad / search / mv as the reference solver leaves them; -DVNL_SOLVER_TAIL keeps it always (regression
+      // build: both forms must give the same bits on every output).
+#ifndef VNL_SOLVER_TAIL
+      if (it + 1 >= MI(iterations) && !trace) {
+        (void)fresh().constraint_force();
+        VNL_PROF(22);
+        break;
+      }
+#endif
       // ---- constraint + gradient update   (gp = grad . Mgrad of the vectors as they stand: carried, see above)
       vreal g = vreal(0.);
       VNL_FOR(d, nv) g += (s[LO(Ma) + d] - s[LO(smooth) + d]) * (s[LO(qacc) + d] - s[LO(qacc_smooth) + d]);
