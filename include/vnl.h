@@ -243,6 +243,36 @@ int vnl_policy_forward(vnl_policy*, const float* params, const float* obs_mean, 
                                                (the reference's policy extras, ppo_networks.py:67-73), or NULL */,
                        void* stream);
 
+/* The same forward pass with the noise drawn INSIDE the kernel, from counter-based streams keyed by
+ * (seed, step, global env index): an env's draws do not depend on the batch size or on its row, so a run sharded over
+ * several devices (env_offset = rank * num_envs) reproduces the unsharded one.  Generator: Philox4x32-10 (Salmon et al.
+ * 2011; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with
+ *   key     = (seed low 32 bits, seed high 32 bits)
+ *   counter = (block, env, step low 32 bits, (step >> 32) << 2 | stream),   step = *step_base + step_offset < 2^62,
+ *   stream  = 0 eps_latent, 1 eps_action, 2 the random action shared by the batch (env word 0xFFFFFFFF),
+ *   env     = env_offset + row.
+ * A call yields four words x0..x3, u_i = ((x_i >> 8) + 0.5) 2^-24; normals by Box-Muller, (u0, u1) -> sqrt(-2 ln u0)
+ * (cos, sin)(2 pi u1) and (u2, u3) likewise; element j of a row is output j % 4 of block j / 4; stream 2 gives 2 u - 1.
+ * ppo_imitation/philox.py restates it in torch ops (the tests' reference).  Everything after the draw is the arithmetic of
+ * vnl_policy_forward: fed the recorded draws, that entry point returns the same bits.
+ * The kernel only READS the step counter (the workgroups of a launch are not ordered against each other): the caller
+ * advances it, in stream order, after the calls that share it -- a captured unroll of T steps bakes step_offset = 0..T-1
+ * into its launches and adds T to *step_base once. */
+typedef struct vnl_policy_noise {
+  uint64_t seed;
+  const int64_t* step_base;   /* device, [1], read only: step = *step_base + step_offset */
+  int64_t step_offset;        /* host value, >= 0 */
+  int64_t env_offset;         /* global index of row 0, >= 0; env_offset + batch < 2^32 - 1 */
+  float *eps_latent_out, *eps_action_out, *rand_action_out; /* optional records of the draws used: [batch][latent],
+                                                              * [batch][act], [act]; the last two stochastic mode only */
+} vnl_policy_noise;
+/* deterministic: stream 0 only.  rand_log_prob NULL: stream 2 is not drawn.  VNL_ERR_ARG (nothing launched) for a null
+ * step_base, a negative offset or an env index that would reach 2^32 - 1. */
+int vnl_policy_forward_noise(vnl_policy*, const float* params, const float* obs_mean, const float* obs_std,
+                             const float* traj, const float* obs, const vnl_policy_noise*, int32_t batch,
+                             int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
+                             float* latent_mean, float* latent_logvar, float* rand_log_prob /* or NULL */, void* stream);
+
 /* ---- rollout post-processing: the training wrappers and the Transition logging in ONE launch ----
  * brax EpisodeWrapper + AutoResetWrapper as applied by the reference's wrap_for_training
  * (ppo_imitation/train.py:204-214) and the per-step Transition of actor_step

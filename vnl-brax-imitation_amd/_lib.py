@@ -81,6 +81,11 @@ class PolicySpec(C.Structure):
     ]
 
 
+class PolicyNoise(C.Structure):  # include/vnl.h: vnl_policy_noise
+    _fields_ = [("seed", C.c_uint64), ("step_base", C.c_void_p), ("step_offset", C.c_int64), ("env_offset", C.c_int64),
+                ("eps_latent_out", C.c_void_p), ("eps_action_out", C.c_void_p), ("rand_action_out", C.c_void_p)]
+
+
 POST_MAX_OPS = 24
 
 
@@ -145,7 +150,7 @@ class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
     "vnl_env_dims", "vnl_env_reset", "vnl_env_step", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
-    "vnl_policy_num_params", "vnl_policy_forward", "vnl_rollout_post", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
+    "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
@@ -196,6 +201,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.vnl_policy_num_params.argtypes = [vp]
         lib.vnl_policy_num_params.restype = C.c_int64
         lib.vnl_policy_forward.argtypes = [vp] + [vp] * 7 + [C.c_int32, C.c_int32] + [vp] * 6 + [vp, vp] + [vp]
+        lib.vnl_policy_forward_noise.argtypes = [vp] + [vp] * 5 + [C.POINTER(PolicyNoise), C.c_int32, C.c_int32] + [vp] * 7 + [vp]
     return lib
 
 

@@ -273,7 +273,68 @@ extern "C" int vnl_policy_profile_stamps(long long* out) {
 
 __device__ __forceinline__ float softplusf(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
-// MODE 0: acting (sampling, no intermediates).  MODE 1: training form -- no sampling, every intermediate the backward pass reads
+// ---- counter-based noise of the acting kernel (MODE 3; include/vnl.h: vnl_policy_noise; restated in ppo_imitation/philox.py)
+struct PolicyNoiseDev {
+  uint32_t key0, key1;      // seed low | high
+  const int64_t* step_base; // device, [1], read only
+  int64_t step_offset;
+  uint32_t env0;            // global index of the batch's row 0
+  float *eps_latent_out, *eps_action_out, *rand_action_out;  // optional records of the draws
+};
+
+// Philox4x32-10 (Salmon et al. 2011)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&x)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
+}
+
+// One Box-Muller pair from two words: u = ((x >> 8) + 0.5) 2^-24 = (2 k + 1) 2^-25 with k = x >> 8.  float32 holds u exactly
+// for k < 2^23 and 1 - u exactly above, so the upper half goes through ln u = log1p(-(1 - u)) and the angle through
+// cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u)): no rounding of u anywhere (rounded to 1 it would
+// turn a radius of 2.4e-4 into 0).
+__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, float& n0, float& n1) {
+  const uint32_t ka = xa >> 8, kb = xb >> 8;
+  const bool ha = ka >= (1u << 23), hb = kb >= (1u << 23);
+  const float da = (float)(ha ? (1u << 25) - 1u - 2u * ka : 2u * ka + 1u) * 0x1p-25f;  // u or 1 - u, exact
+  const float db = (float)(hb ? (1u << 25) - 1u - 2u * kb : 2u * kb + 1u) * 0x1p-25f;
+  const float r = sqrtf(-2.f * (ha ? log1pf(-da) : logf(da)));
+  float sn, cs;
+  sincosf(6.283185307179586f * db, &sn, &cs);
+  n0 = r * cs, n1 = r * (hb ? -sn : sn);
+}
+
+// dst[r][0 .. 4 nb) (LDS, row stride 4 nb) = the standard normal draws of stream `stream` for the tile's rows r < nrow: ONE thread
+// per Philox block (four normals), shared through LDS; rec (optional): [batch][n] record in global memory
+__device__ __forceinline__ void draw_normal_tile(const PolicyNoiseDev& nz, int64_t step, uint32_t stream, int e0, int nrow, int n,
+                                                 float* dst, float* __restrict__ rec) {
+  const int nb = (n + 3) >> 2;
+  const uint32_t c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | stream;
+  for (int i = threadIdx.x; i < nrow * nb; i += PNT) {
+    const int r = i / nb, b = i - r * nb;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)b, nz.env0 + (uint32_t)(e0 + r), c2, c3, nz.key0, nz.key1, x);
+    float v[4];
+    box_muller(x[0], x[1], v[0], v[1]);
+    box_muller(x[2], x[3], v[2], v[3]);
+    *(v4f*)(dst + (r * nb + b) * 4) = v4f{v[0], v[1], v[2], v[3]};
+    if (rec) {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        if (4 * b + q < n) rec[(size_t)(e0 + r) * n + 4 * b + q] = v[q];
+    }
+  }
+}
+
+// MODE 0: acting (sampling, no intermediates).  MODE 3: acting with the noise drawn HERE -- where MODE 0 reads eps_latent[g],
+// eps_action[g] and rand_action[c], MODE 3 reads draws of its own counter-based streams from LDS (the partial-sum buffer P,
+// idle between two Denses); everything after the draw is the same expressions.  MODE 1: training form -- no sampling, every intermediate the backward pass reads
 // goes to t.  MODE 2: training form from the FIRST encoder layer's Dense output on (t.encH[0], made by a GEMM launch of
 // csrc/vnl_ppo.hip): without the 16 x 795 trajectory tile the workgroup's LDS drops from 132 KB to 97 KB, so that workgroups of
 // the value MLP's GEMMs stay resident beside it.
@@ -289,7 +350,8 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
                                                               float* __restrict__ logits, float* __restrict__ lat_mean,
                                                               float* __restrict__ lat_logvar,
                                                               const float* __restrict__ rand_action,
-                                                              float* __restrict__ rand_log_prob, PolicyTrainOut t) {
+                                                              float* __restrict__ rand_log_prob, PolicyTrainOut t,
+                                                              PolicyNoiseDev nz) {
   extern __shared__ __align__(16) float lds[];
   float* A = lds;
   float* B = lds + PT * p.ldA;
@@ -297,7 +359,9 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
   const int e0 = blockIdx.x * PT, tid = threadIdx.x;
   const int nrow = min(PT, batch - e0);
 
-  constexpr bool TRAIN = MODE != 0;
+  constexpr bool TRAIN = MODE == 1 || MODE == 2;
+  constexpr bool DRAW = MODE == 3;
+  const int64_t step = DRAW ? *nz.step_base + nz.step_offset : 0;  // (read only: blocks of a launch are not ordered)
   if (TRAIN) __builtin_amdgcn_s_setprio(3);  // (beside the value MLP's chip-filling GEMMs: this chain is the step's critical path)
   POL_STAMP(0);
   float *X = A, *Y = B;
@@ -339,6 +403,11 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
   }
   POL_STAMP(10);
   if (TRAIN) store_tile(Y, ldy, nrow, 2 * p.latent, t.ml, e0);
+  const int lat4 = (p.latent + 3) & ~3;
+  if (DRAW) {  // stream 0 -> P[r][c]
+    draw_normal_tile(nz, step, 0u, e0, nrow, p.latent, P, nz.eps_latent_out);
+    __syncthreads();
+  }
   // ---- z = mean + eps * exp(logvar / 2) (ipn:73-76); decoder input [z | normalised obs] -> X
   for (int i = tid; i < PT * p.latent; i += PNT) {
     int r = i / p.latent, c = i - r * p.latent;
@@ -347,7 +416,7 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
     if (r < nrow) {
       size_t g = (size_t)(e0 + r) * p.latent + c;
       lat_mean[g] = mu, lat_logvar[g] = lv;
-      z = mu + eps_latent[g] * expf(0.5f * lv);
+      z = mu + (DRAW ? P[r * lat4 + c] : eps_latent[g]) * expf(0.5f * lv);
     }
     X[r * ldx + c] = z;
   }
@@ -386,6 +455,23 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
   }
   if (TRAIN) return;  // (sampling belongs to acting; the loss head works from the logits)
   float* lp = Y;  // per-(env, action) log-prob terms
+  const bool has_rand = DRAW ? rand_log_prob != nullptr : rand_action != nullptr;
+  const int act4 = (na + 3) & ~3;
+  if (DRAW && !deterministic) {  // stream 1 -> P[r][c]; stream 2, ONE draw shared by the batch -> P[PT][c], the same in every workgroup
+    draw_normal_tile(nz, step, 1u, e0, nrow, na, P, nz.eps_action_out);
+    if (has_rand && tid < (act4 >> 2)) {
+      uint32_t x[4];
+      philox4x32_10((uint32_t)tid, 0xFFFFFFFFu, (uint32_t)step, ((uint32_t)(step >> 32) << 2) | 2u, nz.key0, nz.key1, x);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        // 2 u - 1 = (2 k + 1 - 2^24) 2^-24: an odd integer below 2^24 in magnitude, exact in float32 and never -1 or 1
+        const float v = (float)((int)(2u * (x[q] >> 8) + 1u) - (1 << 24)) * 0x1p-24f;
+        P[PT * act4 + 4 * tid + q] = v;
+        if (blockIdx.x == 0 && nz.rand_action_out && 4 * tid + q < na) nz.rand_action_out[4 * tid + q] = v;
+      }
+    }
+    __syncthreads();
+  }
   for (int i = tid; i < PT * na; i += PNT) {
     int r = i / na, c = i - r * na;
     float term = 0.f;
@@ -396,13 +482,13 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
         action[g] = tanhf(loc);  // mode()
       } else {
         float scale = softplusf(X[r * ldx + na + c]) + 0.001f;
-        float eps = eps_action[g];
+        float eps = DRAW ? P[r * act4 + c] : eps_action[g];
         float raw = loc + scale * eps;
         raw_action[g] = raw, action[g] = tanhf(raw);
         // Normal log-pdf minus the tanh log-det-Jacobian 2 (log 2 - x - softplus(-2x))
         term = -0.5f * eps * eps - 0.9189385332046727f - logf(scale) - 2.f * (0.6931471805599453f - raw - softplusf(-2.f * raw));
-        if (rand_action) {  // log-prob of ONE random pre-tanh action shared by all envs (ppo_networks.py:67-73)
-          float x = rand_action[c], z = (x - loc) / scale;
+        if (has_rand) {  // log-prob of ONE random pre-tanh action shared by all envs (ppo_networks.py:67-73)
+          float x = DRAW ? P[PT * act4 + c] : rand_action[c], z = (x - loc) / scale;
           lp[r * ldy + na + c] = -0.5f * z * z - 0.9189385332046727f - logf(scale) - 2.f * (0.6931471805599453f - x - softplusf(-2.f * x));
         }
       }
@@ -414,7 +500,7 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
     float s = 0.f;
     for (int c = 0; c < na; c++) s += lp[tid * ldy + c];
     log_prob[e0 + tid] = s;
-    if (rand_action) {
+    if (has_rand) {
       float s2 = 0.f;
       for (int c = 0; c < na; c++) s2 += lp[tid * ldy + na + c];
       rand_log_prob[e0 + tid] = s2;
@@ -560,6 +646,8 @@ extern "C" int vnl_policy_create(const vnl_policy_spec* s, int32_t max_batch, in
     hipError_t e = hipFuncSetAttribute((const void*)vnl_policy_kernel_t<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)p->lds_bytes);
     if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)vnl_policy_kernel_t<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes);
+    if (e == hipSuccess)
       e = hipFuncSetAttribute((const void*)vnl_policy_kernel_t<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void*)vnl_policy_kernel_t<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes2);
@@ -591,7 +679,40 @@ extern "C" int vnl_policy_forward(vnl_policy* p, const float* params, const floa
   int grid = (batch + PT - 1) / PT;
   hipLaunchKernelGGL(vnl_policy_kernel_t<0>, dim3(grid), dim3(PTHREADS), p->lds_bytes, (hipStream_t)stream, p->d, params,
                      obs_mean, obs_std, traj, obs, eps_latent, eps_action, (int)batch, (int)deterministic, action,
-                     raw_action, log_prob, logits, latent_mean, latent_logvar, rand_action, rand_log_prob, PolicyTrainOut{});
+                     raw_action, log_prob, logits, latent_mean, latent_logvar, rand_action, rand_log_prob, PolicyTrainOut{},
+                     PolicyNoiseDev{});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
+  return VNL_OK;
+}
+
+// The acting kernel drawing its own noise (MODE 3): streams keyed by (seed, step, env_offset + row), see include/vnl.h
+extern "C" int vnl_policy_forward_noise(vnl_policy* p, const float* params, const float* obs_mean, const float* obs_std,
+                                        const float* traj, const float* obs, const vnl_policy_noise* noise, int32_t batch,
+                                        int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
+                                        float* latent_mean, float* latent_logvar, float* rand_log_prob, void* stream) {
+  if (!p || !params || !traj || !obs || !noise || !action || !logits || !latent_mean || !latent_logvar)
+    return pfail(VNL_ERR_ARG, "vnl_policy_forward_noise: null argument");
+  if (!deterministic && (!raw_action || !log_prob))
+    return pfail(VNL_ERR_ARG, "vnl_policy_forward_noise: stochastic mode needs raw_action, log_prob");
+  if (rand_log_prob && deterministic) return pfail(VNL_ERR_ARG, "rand_log_prob: stochastic mode only");
+  if ((obs_mean == nullptr) != (obs_std == nullptr)) return pfail(VNL_ERR_ARG, "obs_mean / obs_std must both be given or both null");
+  if (batch <= 0 || batch > p->max_batch) return pfail(VNL_ERR_ARG, "batch out of range");
+  if (!noise->step_base) return pfail(VNL_ERR_ARG, "vnl_policy_noise: step_base is null (a device pointer to the step counter)");
+  if (noise->step_offset < 0 || noise->env_offset < 0)
+    return pfail(VNL_ERR_ARG, "vnl_policy_noise: step_offset and env_offset must not be negative");
+  if (noise->env_offset + (int64_t)batch >= 0xFFFFFFFFll)
+    return pfail(VNL_ERR_ARG, "vnl_policy_noise: env_offset + batch must stay below 2^32 - 1 (that env index is the shared draw's)");
+  PolicyNoiseDev nz{};
+  nz.key0 = (uint32_t)noise->seed, nz.key1 = (uint32_t)(noise->seed >> 32);
+  nz.step_base = noise->step_base, nz.step_offset = noise->step_offset, nz.env0 = (uint32_t)noise->env_offset;
+  nz.eps_latent_out = noise->eps_latent_out, nz.rand_action_out = deterministic ? nullptr : noise->rand_action_out;
+  nz.eps_action_out = deterministic ? nullptr : noise->eps_action_out;
+  int grid = (batch + PT - 1) / PT;
+  hipLaunchKernelGGL(vnl_policy_kernel_t<3>, dim3(grid), dim3(PTHREADS), p->lds_bytes, (hipStream_t)stream, p->d, params,
+                     obs_mean, obs_std, traj, obs, (const float*)nullptr, (const float*)nullptr, (int)batch, (int)deterministic,
+                     action, raw_action, log_prob, logits, latent_mean, latent_logvar, (const float*)nullptr, rand_log_prob,
+                     PolicyTrainOut{}, nz);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
   return VNL_OK;
@@ -609,11 +730,11 @@ int vnl_policy_forward_train_(vnl_policy* p, const float* params, const float* o
   if (from_first_dense)
     hipLaunchKernelGGL(vnl_policy_kernel_t<2>, dim3(grid), dim3(p->threads2), p->lds_bytes2, (hipStream_t)stream, p->d2, params,
                        obs_mean, obs_std, traj, obs, eps_latent, (const float*)nullptr, (int)batch, 1, (float*)nullptr, (float*)nullptr,
-                       (float*)nullptr, logits, latent_mean, latent_logvar, (const float*)nullptr, (float*)nullptr, *out);
+                       (float*)nullptr, logits, latent_mean, latent_logvar, (const float*)nullptr, (float*)nullptr, *out, PolicyNoiseDev{});
   else
   hipLaunchKernelGGL(vnl_policy_kernel_t<1>, dim3(grid), dim3(PTHREADS), p->lds_bytes, (hipStream_t)stream, p->d, params,
                      obs_mean, obs_std, traj, obs, eps_latent, (const float*)nullptr, (int)batch, 1, (float*)nullptr, (float*)nullptr,
-                     (float*)nullptr, logits, latent_mean, latent_logvar, (const float*)nullptr, (float*)nullptr, *out);
+                     (float*)nullptr, logits, latent_mean, latent_logvar, (const float*)nullptr, (float*)nullptr, *out, PolicyNoiseDev{});
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
   return VNL_OK;

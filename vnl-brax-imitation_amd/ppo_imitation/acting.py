@@ -58,9 +58,24 @@ def _fusable(env):
     return env, ep, base
 
 
+def _device_noise(policy) -> bool:
+    """a policy of make_inference_fn(...)(params, noise="device"): draws keyed by (seed, counter + offset, env index)"""
+    return getattr(policy, "noise", None) == "device"
+
+
+# Private switch (tests compare the two): with a device-noise policy the unroll hands row t of its log buffers to the policy,
+# which writes action / raw_action / log_prob / rand_log_prob / logits there itself; False = the policy allocates its outputs
+# and vnl_rollout_post copies them into the log, as on the generator path.
+_DIRECT_LOG = True
+
+
 def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int, extra_fields) -> Tuple[State, Transition]:
     """Same results as the generic loop below (tests compare the two), 2 launches per step besides the
-    policy: the env step kernel and vnl_rollout_post (which also writes the Transition's observation row)."""
+    policy: the env step kernel and vnl_rollout_post (which also writes the Transition's observation row).
+
+    With a device-noise policy step t draws at `policy.counter + t` and the counter advances by T once, after the loop (one
+    small launch per unroll instead of three noise launches per step; inside a captured graph the offsets are baked in and the
+    add is a node of the graph)."""
     import ctypes as C
 
     from .. import _lib
@@ -101,13 +116,27 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
     n_static = len(ops)
     px_log: Optional[dict] = None
     act_log = None
+    dev_noise = _device_noise(policy)
+    direct = dev_noise and _DIRECT_LOG
+    if direct:  # the policy writes row t of the log itself (contiguous [B, w] slices); the env step reads its action there
+        na = base.action_size
+        f32 = lambda *shape: torch.empty((T, *shape), dtype=torch.float32, device=dev)  # noqa: E731
+        act_log = f32(B, na)
+        px_log = {} if policy.deterministic else {"log_prob": f32(B), "rand_log_prob": f32(B), "raw_action": f32(B, na),
+                                                  "logits": f32(B, 2 * na)}
     for t in range(T):
-        actions, pex = policy(info["traj"], st.obs, key)
+        if direct:
+            actions, pex = policy(info["traj"], st.obs, None, step_offset=t, advance=False,
+                                  out={"action": act_log[t], **{k2: v[t] for k2, v in px_log.items()}})
+        elif dev_noise:
+            actions, pex = policy(info["traj"], st.obs, None, step_offset=t, advance=False)
+        else:
+            actions, pex = policy(info["traj"], st.obs, key)
         base.step(st, actions)
         if px_log is None:
             act_log = new(*actions.shape, like=actions)
             px_log = {k2: new(*v.shape, like=v) for k2, v in pex.items()}
-        step_ops = ops[:n_static] + [(None, actions.contiguous(), None, act_log)] + \
+        step_ops = ops[:n_static] if direct else ops[:n_static] + [(None, actions.contiguous(), None, act_log)] + \
             [(None, v.contiguous(), None, px_log[k2]) for k2, v in pex.items()]
         assert len(step_ops) <= _lib.POST_MAX_OPS
         d.num_ops = len(step_ops)
@@ -122,6 +151,8 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
         d.log_truncation = ptr(sx_log["truncation"][t]) if "truncation" in sx_log else C.c_void_p(0)
         _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
         _generate_unroll_fused.hold = keep  # the launch is asynchronous: keep this step's sources alive
+    if dev_noise:
+        policy.counter.add_(T)
     obs_log = torch.cat((obs0[None], nobs_log[:-1]), dim=0)
     data = Transition(observation=obs_log, action=act_log, reward=rew_log, discount=disc_log, next_observation=nobs_log,
                       extras={"policy_extras": px_log, "state_extras": sx_log})
@@ -138,7 +169,10 @@ class GraphedUnroll:
     The graph works on fixed buffers: `env_state` (the env mutates it in place), the policy's parameter tensors (update them
     IN PLACE between replays: the trainer's flat parameter buffer already is; a normaliser state must be copied into the one
     given here) and the returned Transition, whose tensors are overwritten by the next replay.  `key` must be a generator
-    on the device; it is registered with the graph, so every replay continues its stream as eager calls would."""
+    on the device; it is registered with the graph, so every replay continues its stream as eager calls would.
+
+    With a device-noise policy (make_policy(..., noise="device")) `key` is not used and no generator is registered: the
+    launches carry step offsets 0..T-1 and the graph's last node adds T to `policy.counter`, the only state of the noise."""
 
     def __init__(self, env, env_state: State, policy, key: torch.Generator, unroll_length: int,
                  extra_fields: Sequence[str] = ()):
@@ -146,13 +180,14 @@ class GraphedUnroll:
         dev = env_state.obs.device
         if fz is None or dev.type != "cuda":
             raise ValueError("GraphedUnroll needs AutoResetWrapper(EpisodeWrapper(<env on a HIP device>)), action_repeat 1")
-        if key is None or key.device.type != "cuda":
+        dev_noise = _device_noise(policy)
+        if not dev_noise and (key is None or key.device.type != "cuda"):
             raise ValueError("GraphedUnroll needs a torch.Generator on the device (its stream is captured with the graph)")
         self._args = (fz, env_state, policy, key, int(unroll_length), tuple(extra_fields))
         self.state = env_state
         # warm-up on a side stream (library handles, the policy's kernel object, allocator pools), with the generator and the
         # env state put back afterwards: building the graph must not consume randomness or advance the envs
-        gen_state = key.get_state()
+        gen_state = policy.counter.clone() if dev_noise else key.get_state()
         saved = _snapshot_state(env_state)
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -161,9 +196,12 @@ class GraphedUnroll:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         _restore_state(env_state, saved)
-        key.set_state(gen_state)
         self.graph = torch.cuda.CUDAGraph()
-        self.graph.register_generator_state(key)
+        if dev_noise:
+            policy.counter.copy_(gen_state)
+        else:
+            key.set_state(gen_state)
+            self.graph.register_generator_state(key)
         with torch.cuda.graph(self.graph):
             _, self.data = _generate_unroll_fused(*self._args)
         self._hold = getattr(_generate_unroll_fused, "hold", None)

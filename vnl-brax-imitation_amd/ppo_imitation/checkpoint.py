@@ -7,6 +7,7 @@ brax.io.model pickles the pytree).  Here the same pair goes to one `.npz` (NumPy
     normalizer/{count,mean,summed_variance,std}
     policy/params/<flax path>            e.g. policy/params/encoder/hidden_0/kernel   (Dense kernels stay (in, out))
     [value/params/<flax path>, optimizer/{mu,nu,count}, meta/env_steps]   full training state, for resume
+    [meta/policy_counter]                the acting policy's noise step counter (train(policy_noise="device"))
 
 The tensor names are the reference's Flax tree (intention_policy_network.py:20-136), so a reference checkpoint
 converted to nested dicts of arrays maps 1:1 through `from_flax_tree` / `to_flax_tree`.
@@ -72,7 +73,7 @@ def _flatten(prefix: str, layout: ParamLayout, flat: torch.Tensor, out: Dict[str
 
 def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsState, torch.Tensor], ppo_network,
                 *, value_params: Optional[torch.Tensor] = None, optimizer_state: Optional[Dict[str, torch.Tensor]] = None,
-                env_steps: Optional[int] = None) -> str:
+                env_steps: Optional[int] = None, policy_counter: Optional[torch.Tensor] = None) -> str:
     """`params` = the inference pair the reference saves; the keyword extras make the file resumable."""
     norm, policy = params
     out: Dict[str, np.ndarray] = {f"normalizer/{k}": getattr(norm, k).detach().cpu().numpy() for k in _NORM}
@@ -84,6 +85,8 @@ def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsSta
             out[f"optimizer/{k}"] = v.detach().cpu().numpy()
     if env_steps is not None:
         out["meta/env_steps"] = np.asarray(env_steps, dtype=np.int64)
+    if policy_counter is not None:
+        out["meta/policy_counter"] = policy_counter.detach().cpu().numpy().astype(np.int64).reshape(1)
     if not path.endswith(".npz"):
         path += ".npz"
     np.savez(path, **out)
@@ -179,7 +182,7 @@ def convert_brax_params(pickle_path: str, ppo_network, npz_path: Optional[str] =
 
 
 def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
-    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps'}."""
+    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps', 'policy_counter'}."""
     z = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
     t = lambda a: torch.from_numpy(np.asarray(a)).to(device) if device is not None else torch.from_numpy(np.asarray(a))  # noqa: E731
     norm = running_statistics.RunningStatisticsState(*(t(z[f"normalizer/{k}"]) for k in _NORM))
@@ -191,4 +194,6 @@ def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
         out["optimizer"] = opt
     if "meta/env_steps" in z.files:
         out["env_steps"] = int(z["meta/env_steps"])
+    if "meta/policy_counter" in z.files:
+        out["policy_counter"] = t(z["meta/policy_counter"])
     return out

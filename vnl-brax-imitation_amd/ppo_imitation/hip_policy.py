@@ -72,3 +72,59 @@ class HipIntentionPolicy:
         if rlp is not None:
             extras["rand_log_prob"] = rlp
         return action, {**extras, "latent_mean": lat_mean, "latent_logvar": lat_logvar}
+
+    @torch.no_grad()
+    def forward_noise(self, params: torch.Tensor, obs_mean: Optional[torch.Tensor], obs_std: Optional[torch.Tensor],
+                      traj: torch.Tensor, obs: torch.Tensor, counter: torch.Tensor, step_offset: int = 0, seed: int = 0,
+                      env_offset: int = 0, deterministic: bool = False, rand: bool = True, out: Optional[dict] = None,
+                      eps_out: Optional[dict] = None) -> Tuple[torch.Tensor, dict]:
+        """vnl_policy_forward_noise: the kernel draws eps_latent, eps_action and the shared random action itself, from
+        streams keyed by (seed, *counter + step_offset, env_offset + row).  Nothing is owned here: `counter` is the caller's
+        int64 [1] device tensor, which the kernel only reads (advance it after the calls that share it).
+        `out`: optional preallocated contiguous float32 tensors "action", "raw_action", "log_prob", "rand_log_prob", "logits"
+        (e.g. rows of an unroll's log buffers) written instead of fresh ones; `eps_out`: optional "eps_latent" [B, latent],
+        "eps_action" [B, act], "rand_action" [act] that record the draws used.  `rand=False`: no rand_log_prob."""
+        B, na, nl = obs.shape[0], self.action_size, self.net.latents
+        f32 = dict(dtype=torch.float32, device=obs.device)
+        c = lambda t: t.contiguous()  # noqa: E731
+        traj, obs, params = c(traj), c(obs), c(params)
+        if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != obs.device:
+            raise ValueError("counter must be an int64 tensor of one element on the inputs' device")
+        out, eps_out = out or {}, eps_out or {}
+
+        def buf(name, shape, wanted=True):
+            if not wanted:
+                return None
+            t = out.get(name)
+            if t is None:
+                return torch.empty(shape, **f32)
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != obs.device:
+                raise ValueError(f"out[{name!r}] must be a contiguous float32 {shape} tensor on the inputs' device")
+            return t
+
+        stochastic = not deterministic
+        action, logits = buf("action", (B, na)), buf("logits", (B, 2 * na))
+        lat_mean, lat_logvar = torch.empty((B, nl), **f32), torch.empty((B, nl), **f32)
+        raw, lp = buf("raw_action", (B, na), stochastic), buf("log_prob", (B,), stochastic)
+        rlp = buf("rand_log_prob", (B,), stochastic and rand)
+        rec = {k: eps_out.get(k) for k in ("eps_latent", "eps_action", "rand_action")}
+        for k, shape in (("eps_latent", (B, nl)), ("eps_action", (B, na)), ("rand_action", (na,))):
+            t = rec[k]
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"eps_out[{k!r}] must be a contiguous float32 {shape} tensor")
+        if obs_mean is not None:
+            obs_mean, obs_std = c(obs_mean), c(obs_std)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        nz = _lib.PolicyNoise()
+        nz.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        nz.step_base, nz.step_offset, nz.env_offset = p(counter), int(step_offset), int(env_offset)
+        nz.eps_latent_out, nz.eps_action_out, nz.rand_action_out = p(rec["eps_latent"]), p(rec["eps_action"]), p(rec["rand_action"])
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        _lib.check(self.lib, self.lib.vnl_policy_forward_noise(
+            self.h, p(params), p(obs_mean), p(obs_std), p(traj), p(obs), C.byref(nz), B, int(deterministic), p(action), p(raw),
+            p(lp), p(logits), p(lat_mean), p(lat_logvar), p(rlp), stream))
+        self._hold = (traj, obs, params, obs_mean, obs_std, counter, rec)
+        extras = {} if deterministic else {"log_prob": lp, "raw_action": raw, "logits": logits}
+        if rlp is not None:
+            extras["rand_log_prob"] = rlp
+        return action, {**extras, "latent_mean": lat_mean, "latent_logvar": lat_logvar}

@@ -1,0 +1,83 @@
+"""Counter-based noise of the acting policy: Philox4x32-10 (Salmon et al. 2011, "Parallel random numbers: as easy as
+1, 2, 3") restated in torch integer ops.  It is the reference of the device draws of csrc/vnl_policy.hip
+(vnl_policy_forward_noise) and what the torch-backend policy draws from with `noise="device"`.
+
+    key     = (seed low 32 bits, seed high 32 bits)
+    counter = (block, env, step low 32 bits, (step >> 32) << 2 | stream),  step < 2^62
+    stream  = 0 latent draw, 1 action draw, 2 the random action shared by the batch (env = 0xFFFFFFFF)
+
+A call yields four words x0..x3; u_i = ((x_i >> 8) + 0.5) 2^-24 lies strictly inside (0, 1).  Normal draws are Box-Muller
+pairs, (u0, u1) -> sqrt(-2 ln u0) (cos, sin)(2 pi u1) and (u2, u3) likewise; element j of an env's row is output j % 4 of block
+j / 4, the surplus of the last block is dropped.  Stream 2 gives 2 u - 1 per element.  An env's draws depend on
+(seed, step, global env index) alone: not on the batch size, not on where the env sits in the batch.
+
+Words are int64 tensors masked to 32 bits; the floating-point part runs in float64 and is cast to float32 last."""
+from __future__ import annotations
+
+import math
+from typing import Tuple, Union
+
+import torch
+
+M0, M1 = 0xD2511F53, 0xCD9E8D57
+W0, W1 = 0x9E3779B9, 0xBB67AE85
+MASK = 0xFFFFFFFF
+STREAM_LATENT, STREAM_ACTION, STREAM_SHARED = 0, 1, 2
+SHARED_ENV = 0xFFFFFFFF  # the env word of stream 2: no env may have this index
+
+IntLike = Union[int, torch.Tensor]
+
+
+def _mulhilo(m: int, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(high, low) 32 bits of the 64-bit product m * x, without leaving the signed 64-bit range: x in 16-bit halves."""
+    p0, p1 = m * (x & 0xFFFF), m * (x >> 16)  # both < 2^48
+    lo = (((p1 & 0xFFFF) << 16) + p0) & MASK
+    hi = (p1 + (p0 >> 16)) >> 16
+    return hi, lo
+
+
+def philox4x32(counter: torch.Tensor, key: Tuple[IntLike, IntLike], rounds: int = 10) -> torch.Tensor:
+    """counter: int64 [..., 4] of 32-bit words; key: two 32-bit words (ints or int64 tensors).  Returns int64 [..., 4]."""
+    c0, c1, c2, c3 = (counter[..., i] & MASK for i in range(4))
+    k0, k1 = key
+    for r in range(rounds):
+        hi0, lo0 = _mulhilo(M0, c0)
+        hi1, lo1 = _mulhilo(M1, c2)
+        c0, c1, c2, c3 = (hi1 ^ c1 ^ k0) & MASK, lo1, (hi0 ^ c3 ^ k1) & MASK, lo0
+        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
+    return torch.stack((c0, c1, c2, c3), dim=-1)
+
+
+def _words(seed: int, step: IntLike, env: torch.Tensor, n: int, stream: int) -> torch.Tensor:
+    """The (n + 3) // 4 blocks of every env's row: int64 [len(env), blocks, 4].  `step` may be an int64 tensor on the
+    device (the policy's counter): nothing is read back to the host."""
+    dev = env.device
+    nb = (n + 3) // 4
+    step = torch.as_tensor(step, dtype=torch.int64, device=dev).reshape(())
+    shape = (env.shape[0], nb)
+    ctr = torch.stack((torch.arange(nb, dtype=torch.int64, device=dev).expand(shape),
+                       (env.to(torch.int64) & MASK)[:, None].expand(shape),
+                       (step & MASK).expand(shape),
+                       (((step >> 32) << 2) | stream).expand(shape)), dim=-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return philox4x32(ctr, (seed & MASK, seed >> 32))
+
+
+def _unit(x: torch.Tensor) -> torch.Tensor:
+    return ((x >> 8).to(torch.float64) + 0.5) * 2.0 ** -24
+
+
+def normal(seed: int, step: IntLike, env: torch.Tensor, n: int, stream: int) -> torch.Tensor:
+    """float32 [len(env), n] standard normal draws of the envs with GLOBAL indices `env` (int64 [B]) at `step`."""
+    u = _unit(_words(seed, step, env, n, stream))
+    r = torch.sqrt(-2.0 * torch.log(u[..., 0::2]))  # [B, blocks, 2]: from u0, u2
+    a = (2.0 * math.pi) * u[..., 1::2]              # from u1, u3
+    out = torch.stack((r * torch.cos(a), r * torch.sin(a)), dim=-1)  # [B, blocks, pair, (cos, sin)]
+    return out.reshape(env.shape[0], -1)[:, :n].to(torch.float32)
+
+
+def shared_uniform(seed: int, step: IntLike, n: int, device=None) -> torch.Tensor:
+    """float32 [n] in (-1, 1): the ONE pre-tanh random action shared by the batch (reference ppo_networks.py:67-73)."""
+    env = torch.full((1,), SHARED_ENV, dtype=torch.int64, device=device)
+    u = _unit(_words(seed, step, env, n, STREAM_SHARED))
+    return (2.0 * u - 1.0).reshape(-1)[:n].to(torch.float32)

@@ -15,7 +15,7 @@ from typing import Any, Callable, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import distribution, running_statistics
+from . import distribution, philox, running_statistics
 from . import intention_policy_network as ipn
 
 
@@ -121,6 +121,85 @@ def _rand_action(n: int, key: Optional[torch.Generator], device) -> torch.Tensor
     return torch.empty((n,), dtype=torch.float32, device=device).uniform_(-1.0, 1.0, generator=key)  # one launch, not three
 
 
+_LOGGED = ("log_prob", "rand_log_prob", "raw_action", "logits")  # the policy extras of a stochastic call, in this order
+
+
+class _DeviceNoisePolicy:
+    """make_inference_fn(...)(params, noise="device"): the acting policy with counter-based noise (philox.py).
+
+    `policy(traj, obs)` is the usual call.  An unroll that steps the counter itself passes `step_offset=t, advance=False`
+    (and adds T to `policy.counter` once, afterwards) and may hand in `out`: preallocated contiguous tensors for "action" and
+    the policy extras, which the call then writes instead of allocating its own."""
+
+    noise = "device"
+
+    def __init__(self, nets: PPOImitationNetworks, hip_cache: dict, params, deterministic: bool, use_hip: bool, seed: int,
+                 env_offset: int, counter: Optional[torch.Tensor]):
+        self.nets, self.hip_cache, self.params = nets, hip_cache, params
+        self.deterministic, self.use_hip = bool(deterministic), use_hip
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        if self.env_offset < 0:
+            raise ValueError("env_offset must not be negative")
+        dev = params[1].device
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != dev:
+            raise ValueError("counter must be an int64 tensor of one element on the parameters' device")
+        self.counter = counter
+
+    @torch.no_grad()
+    def __call__(self, trajectories: torch.Tensor, observations: torch.Tensor, key_sample=None, *, step_offset: int = 0,
+                 advance: bool = True, out: Optional[dict] = None) -> Tuple[torch.Tensor, dict]:
+        if observations.dim() != 2:
+            raise ValueError("noise='device' keys the draws by the row: observations must be (batch, obs_size)")
+        res = (self._hip if self.use_hip else self._torch)(trajectories, observations, int(step_offset), out)
+        if advance:
+            self.counter.add_(1)
+        return res
+
+    def _hip(self, trajectories, observations, step_offset, out):
+        from .hip_policy import HipIntentionPolicy
+
+        nets, dist = self.nets, self.nets.parametric_action_distribution
+        normalizer_params, policy_params = self.params
+        dev, B = observations.device, observations.shape[0]
+        k = (dev, B)
+        if k not in self.hip_cache:
+            self.hip_cache[k] = HipIntentionPolicy(nets.policy_module, dist.event_size, B, dev)
+        mean = std = None
+        if nets.normalizes and normalizer_params is not None:
+            mean, std = normalizer_params.mean, normalizer_params.std
+        action, extras = self.hip_cache[k].forward_noise(
+            policy_params.detach(), mean, std, trajectories, observations, self.counter, step_offset=step_offset,
+            seed=self.seed, env_offset=self.env_offset, deterministic=self.deterministic, out=out)
+        if self.deterministic:
+            return action, {}
+        return action, {k2: extras[k2] for k2 in _LOGGED}
+
+    def _torch(self, trajectories, observations, step_offset, out):
+        nets, dist = self.nets, self.nets.parametric_action_distribution
+        normalizer_params, policy_params = self.params
+        dev, B = observations.device, observations.shape[0]
+        if self.env_offset + B >= philox.SHARED_ENV:
+            raise ValueError("env_offset + batch must stay below 2^32 - 1")
+        step = self.counter.to(dev) + step_offset
+        env = self.env_offset + torch.arange(B, dtype=torch.int64, device=dev)
+        eps_latent = philox.normal(self.seed, step, env, nets.policy_module.latents, philox.STREAM_LATENT)
+        logits, _, _ = nets.policy_network.apply(normalizer_params, policy_params, trajectories, observations, eps_latent)
+        if self.deterministic:
+            res = {"action": dist.mode(logits)}
+        else:
+            eps_action = philox.normal(self.seed, step, env, dist.event_size, philox.STREAM_ACTION)
+            raw_actions = dist.sample_no_postprocessing(logits, eps_action)
+            random_actions = philox.shared_uniform(self.seed, step, dist.event_size, device=dev)
+            res = {"action": dist.postprocess(raw_actions), "log_prob": dist.log_prob(logits, raw_actions),
+                   "rand_log_prob": dist.log_prob(logits, random_actions.expand_as(raw_actions)),
+                   "raw_action": raw_actions, "logits": logits}
+        if out is not None:
+            res = {k2: out[k2].copy_(v) for k2, v in res.items()}
+        return res["action"], {k2: res[k2] for k2 in _LOGGED if k2 in res}
+
+
 def make_inference_fn(ppo_networks: PPOImitationNetworks):
     """ppo_networks.py:35-87.  `key_sample` is a torch.Generator (or None for the global one);
     the JAX threefry stream is not reproduced, the sampling structure is:
@@ -130,14 +209,26 @@ def make_inference_fn(ppo_networks: PPOImitationNetworks):
 
     hip_cache = {}
 
-    def make_policy(params, deterministic: bool = False, backend: str = "auto"):
+    def make_policy(params, deterministic: bool = False, backend: str = "auto", noise: str = "generator", seed: int = 0,
+                    env_offset: int = 0, counter: Optional[torch.Tensor] = None):
         """backend: "hip" = fused MFMA inference kernel (vnl_policy_forward), "torch" = hipBLASLt ops,
         "auto" = hip on a HIP device when the observation preprocessor is the running-statistics
-        normaliser or the identity."""
+        normaliser or the identity.
+
+        noise: "generator" = the three draws come from `key_sample`, batch-shaped (an env's noise depends on the batch size
+        and on its row); "device" = counter-based streams keyed by (seed, step, env_offset + row) (philox.py): the HIP kernel
+        draws its own noise (vnl_policy_forward_noise), the torch backend draws from the restatement, and `key_sample` is
+        ignored.  The returned policy then holds `policy.counter`, an int64 [1] tensor beside the parameters: a call draws
+        at step `counter`, then advances it by one (`counter`: continue an existing one instead of starting at 0;
+        checkpoint it to resume a run).  `env_offset`: global index of row 0 (rank * num_envs of a sharded run)."""
         normalizer_params, policy_params = params
         dist = ppo_networks.parametric_action_distribution
         latent = ppo_networks.policy_module.latents
         use_hip = backend == "hip" or (backend == "auto" and policy_params.is_cuda and ppo_networks.hip_ok)
+        if noise not in ("generator", "device"):
+            raise ValueError(f"noise must be 'generator' or 'device', got {noise!r}")
+        if noise == "device":
+            return _DeviceNoisePolicy(ppo_networks, hip_cache, params, deterministic, use_hip, seed, env_offset, counter)
 
         @torch.no_grad()
         def policy_hip(trajectories, observations, key_sample=None):

@@ -40,6 +40,7 @@ class TrainingState:
     params: torch.Tensor  # flat [policy | value]
     normalizer_params: running_statistics.RunningStatisticsState
     env_steps: int
+    policy_counter: Optional[torch.Tensor] = None  # policy_noise="device": the acting policy's step counter, int64 [1]
 
 
 class FlatAdam:
@@ -142,6 +143,7 @@ def train(
     capture_graph: Optional[bool] = None,
     restore_from: Optional[str] = None,
     update_backend: str = "auto",
+    policy_noise: str = "generator",
 ):
     """PPO training (train.py:62-491).
 
@@ -162,6 +164,13 @@ def train(
     (RodentTracking.with_domain), drawn once and fixed for the run.  The training env gets num_envs = the per-rank batch and
     a generator seeded from `seed` (the same on every rank), the eval env num_eval_envs and a generator of the eval seed
     (bind_randomization).
+
+    `policy_noise`: "generator" = the acting policy's noise comes from this rank's torch.Generator, batch-shaped; "device" =
+    counter-based streams keyed by (seed, step, global env index) (ppo_networks.make_inference_fn, philox.py): the training
+    policy uses key `seed` and env_offset = rank * (num_envs // world), so the rollout noise of env e does not depend on how
+    the envs are sharded; the eval policy uses key `seed + 1` and a counter of its own.  The training counter is
+    `TrainingState.policy_counter` (checkpoint.save_params(policy_counter=...) / `restore_from` carry it).  The PPO update's
+    per-minibatch draws stay on the generator.
 
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
@@ -198,6 +207,13 @@ def train(
     ppo_network = network_factory(env_state.info["traj"].shape[-1], env_state.obs.shape[-1], env.action_size,
                                   preprocess_observations_fn=normalize)
     make_policy = ppo_networks.make_inference_fn(ppo_network)
+    assert policy_noise in ("generator", "device")
+    act_kw: Dict[str, Any] = {}   # keywords of the training policy / the eval policy
+    eval_kw: Dict[str, Any] = {}
+    if policy_noise == "device":
+        act_kw = dict(noise="device", seed=seed, env_offset=rank * local_envs,
+                      counter=torch.zeros(1, dtype=torch.int64, device=device))
+        eval_kw = dict(noise="device", seed=seed + 1, counter=torch.zeros(1, dtype=torch.int64, device=device))
 
     n_pol, n_val = ppo_network.policy_network.layout.size, ppo_network.value_network.layout.size
     flat = torch.cat([ppo_network.policy_network.init(g_net), ppo_network.value_network.init(g_net)]).to(device)
@@ -210,6 +226,7 @@ def train(
         params=flat,
         normalizer_params=running_statistics.init_state(env_state.obs.shape[-1], device=device),
         env_steps=0,
+        policy_counter=act_kw.get("counter"),
     )
 
     if restore_from is not None:
@@ -224,6 +241,8 @@ def train(
                 training_state.optimizer_state[k].copy_(v)
         training_state.normalizer_params = ck["params"][0]
         training_state.env_steps = ck.get("env_steps", 0)
+        if training_state.policy_counter is not None and "policy_counter" in ck:
+            training_state.policy_counter.copy_(ck["policy_counter"])
 
     from .intention_policy_network import LeafParams
 
@@ -463,7 +482,7 @@ def train(
         nonlocal env_state
         use_graph = (capture_graph and device.type == "cuda" and g_dev is not g_env and acting._fusable(env) is not None)
         if not use_graph:
-            policy = make_policy((training_state.normalizer_params, training_state.params.detach()[:n_pol]))
+            policy = make_policy((training_state.normalizer_params, training_state.params.detach()[:n_pol]), **act_kw)
             out = []
             for _ in range(n_chunks):
                 env_state, data = acting.generate_unroll(env, env_state, policy, g_dev, unroll_length,
@@ -473,8 +492,9 @@ def train(
         g = graphed_roll
         if not g or g["unroll"].state is not env_state:  # (a fresh State after `env.reset`: the graph is bound to its buffers)
             g["norm"] = training_state.normalizer_params.clone()
-            g["unroll"] = acting.GraphedUnroll(env, env_state, make_policy((g["norm"], training_state.params.detach()[:n_pol])),
-                                               g_dev, unroll_length, extra_fields=("truncation", "traj"))
+            roll_policy = make_policy((g["norm"], training_state.params.detach()[:n_pol]), **act_kw)
+            g["unroll"] = acting.GraphedUnroll(env, env_state, roll_policy, g_dev, unroll_length,
+                                               extra_fields=("truncation", "traj"))
         for f in ("count", "mean", "summed_variance", "std"):
             getattr(g["norm"], f).copy_(getattr(training_state.normalizer_params, f))
         out = []
@@ -551,7 +571,7 @@ def train(
         ev_wrapped = env_wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat,
                                        randomization_fn=bind_randomization(randomization_fn, num_eval_envs, seed * 31 + 7),
                                        reset_info_on_autoreset=reset_info_on_autoreset)
-        evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval),
+        evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval, **eval_kw),
                                      num_eval_envs=num_eval_envs, episode_length=episode_length,
                                      action_repeat=action_repeat, key=g_eval)
 
