@@ -379,7 +379,8 @@ int64_t vnl_ppo_update_num_params(const vnl_ppo_update*);
  * "latent_mean", "latent_logvar" [T*B][latent] */
 int vnl_ppo_update_buffer(const vnl_ppo_update*, const char* name, float** dev_ptr, int64_t* count);
 /* metrics [9]: [0..8) as vnl_ppo_head, [8] prediction_corr -- the mean of corrcoef([vs ; reward * reward_scaling]) over
- * its (2T)^2 entries (reference intention_losses.py:186-188); 0 when 2T * B floats exceed 60 KB of LDS */
+ * its (2T)^2 entries (reference intention_losses.py:186-188), computed at every minibatch size (vnl_prediction_corr below,
+ * route_request 0) */
 int vnl_ppo_minibatch_grad(vnl_ppo_update*, const float* params, const vnl_ppo_batch*, const vnl_ppo_hparams*, float* grads,
                            float* metrics, void* stream);
 /* The same step in two parts, for data-parallel training (reference ppo_imitation/train.py:251-268 averages the gradient over the
@@ -389,6 +390,23 @@ int vnl_ppo_minibatch_grad(vnl_ppo_update*, const float* params, const vnl_ppo_b
  * exchange overlaps part 2.  part 0 = the whole step (== vnl_ppo_minibatch_grad). */
 int vnl_ppo_minibatch_grad_part(vnl_ppo_update*, const float* params, const vnl_ppo_batch*, const vnl_ppo_hparams*, float* grads,
                                 float* metrics, void* stream, int part);
+
+/* ---- prediction_corr on its own: the mean over the (2T)^2 entries of corrcoef([vs ; reward * reward_scaling]), two-pass
+ * like jnp.corrcoef (row means, then the Gram matrix of the centred rows; entries clamped to [-1, 1], a NaN passed through).
+ * `vs`, `reward`: time-major [T][B] float32 device buffers; `out`: one float on the device.  Route 1 is one workgroup with all
+ * 2T rows in LDS ((2 T B + 2 T) * 4 <= 61440 bytes); route 2 splits B over `chunks` workgroups per pair of 64-row tiles
+ * (`chunk_cols` columns each, partial Gram matrices in `workspace`, summed in ascending chunk order: no atomics, the same
+ * bits on every call).  Everything is enqueued on `stream`; no host synchronisation, no allocation (capturable).
+ * route_request: 0 = what vnl_ppo_minibatch_grad takes, 1 / 2 = force (1 -> VNL_ERR_ARG when the rows do not fit).
+ * `workspace` needs vnl_corr_plan.workspace_floats floats (0 for route 1: it may then be NULL). */
+typedef struct vnl_corr_plan {
+  int32_t route; /* 1 one workgroup, 2 tiled */
+  int32_t chunks, chunk_cols, row_tiles; /* route 2 (0 for route 1) */
+  int64_t workspace_floats;
+} vnl_corr_plan;
+int vnl_prediction_corr_plan(int32_t T, int32_t B, int32_t route_request, vnl_corr_plan* out); /* needs no device */
+int vnl_prediction_corr(const float* vs, const float* reward, float reward_scaling, int32_t T, int32_t B, int32_t route_request,
+                        float* workspace, int64_t workspace_floats, float* out, void* stream);
 
 #ifdef __cplusplus
 }

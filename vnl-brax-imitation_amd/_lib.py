@@ -140,6 +140,10 @@ class PPOHParams(C.Structure):  # include/vnl.h: vnl_ppo_hparams
                                          "clipping_epsilon", "kl_weight", "min_std", "var_scale")] + \
                [("normalize_advantage", C.c_int32), ("pad_", C.c_int32)]
 
+class CorrPlan(C.Structure):  # include/vnl.h: vnl_corr_plan
+    _fields_ = [(n, C.c_int32) for n in ("route", "chunks", "chunk_cols", "row_tiles")] + [("workspace_floats", C.c_int64)]
+
+
 class Domain(C.Structure):  # include/vnl.h: vnl_domain (float64 device pointers, [num_envs][n]; null = the model's value)
     _fields_ = [(n, C.c_void_p) for n in ("cg_friction", "act_gain", "dof_damping", "dof_armature")]
 
@@ -155,8 +159,9 @@ EXPORTS = (
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
     "vnl_env_set_domain", "vnl_env_set_body_domain",
+    "vnl_prediction_corr_plan", "vnl_prediction_corr",
 )
-_HIP_ONLY = ("vnl_policy_", "vnl_ppo_update_", "vnl_ppo_minibatch_")  # not in the test-only host simulation
+_HIP_ONLY = ("vnl_policy_", "vnl_ppo_update_", "vnl_ppo_minibatch_", "vnl_prediction_corr")  # not in the test-only host simulation
 
 
 class VnlError(RuntimeError):
@@ -194,6 +199,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.vnl_ppo_update_buffer.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64)]
         lib.vnl_ppo_minibatch_grad.argtypes = [vp, vp, C.POINTER(PPOBatch), C.POINTER(PPOHParams), vp, vp, vp]
         lib.vnl_ppo_minibatch_grad_part.argtypes = [vp, vp, C.POINTER(PPOBatch), C.POINTER(PPOHParams), vp, vp, vp, C.c_int]
+        lib.vnl_prediction_corr_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CorrPlan)]
+        lib.vnl_prediction_corr.argtypes = [vp, vp, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp]
     if hasattr(lib, "vnl_policy_create"):
         lib.vnl_policy_create.argtypes = [C.POINTER(PolicySpec), C.c_int32, C.c_int32, C.POINTER(vp)]
         lib.vnl_policy_destroy.argtypes = [vp]

@@ -746,6 +746,192 @@ __global__ void __launch_bounds__(VNL_CORR_THREADS) prediction_corr_kernel(const
   if (tid == 0) *out = red[0] / (float)(R * R);
 }
 
+// The same metric at any size (the rows of a large minibatch do not fit one workgroup's LDS): two-pass like jnp.corrcoef, in
+// three launches.  (a) row means; (b) the Gram matrix of the centred rows, split over B: workgroup (pair of 64-row tiles,
+// chunk of columns) stages centred 64 x 32 slabs in LDS and writes its partial block -- and, off the diagonal, the block's
+// mirror image -- into its chunk's R x R matrix; (c) one workgroup adds the partial matrices in ascending chunk order,
+// normalises, clamps and averages.  No atomics: every sum has a fixed order, so a replayed graph and two data-parallel
+// replicas produce the same bits.  Workspace: [R means][R squared norms][chunks][R][R].
+#define VNL_CORR_TILE 64                    /* rows of a tile: 256 threads x (4 x 4) entries each */
+#define VNL_CORR_SLAB 32                    /* columns staged at a time */
+#define VNL_CORR_LD (VNL_CORR_SLAB + 1)     /* odd row stride: the sixteen rows a wave reads in one step sit in sixteen banks */
+#define VNL_CORR_MAX_CHUNKS 32
+__device__ __forceinline__ float corr_row_value(const float* vs, const float* reward, float scale, int T, int B, int r, int c) {
+  return r < T ? vs[(size_t)r * B + c] : reward[(size_t)(r - T) * B + c] * scale;
+}
+
+__global__ void __launch_bounds__(256) prediction_corr_mean_kernel(const float* vs, const float* reward, float scale, int T, int B,
+                                                                   float* mean) {
+  __shared__ float red[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  float s = 0.f;
+  for (int c = tid; c < B; c += 256) s += corr_row_value(vs, reward, scale, T, B, r, c);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) mean[r] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)B;
+}
+
+__global__ void __launch_bounds__(256) prediction_corr_gram_kernel(const float* vs, const float* reward, float scale, int T, int B,
+                                                                   int chunk_cols, const float* mean, float* part) {
+  __shared__ float xs[2][VNL_CORR_TILE * VNL_CORR_LD];
+  const int R = 2 * T, nt = (R + VNL_CORR_TILE - 1) / VNL_CORR_TILE, tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+  int ti = 0, rem = blockIdx.x;  // the pair (ti <= tj) of row tiles: the upper triangle, row by row
+  while (rem >= nt - ti) rem -= nt - ti, ti++;
+  const int tj = ti + rem, chunk = blockIdx.y;
+  const int c0 = chunk * chunk_cols, c1 = c0 + chunk_cols < B ? c0 + chunk_cols : B;
+  const float* xi = xs[0];
+  const float* xj = xs[ti == tj ? 0 : 1];
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++) acc[a][b] = 0.f;
+  for (int s0 = c0; s0 < c1; s0 += VNL_CORR_SLAB) {
+    // centred slab(s) into LDS; rows past R and columns past the chunk are zeros, so the product loop has constant bounds
+    for (int h = 0; h < (ti == tj ? 1 : 2); h++) {
+      const int row0 = (h == 0 ? ti : tj) * VNL_CORR_TILE;
+      for (int e = tid; e < VNL_CORR_TILE * VNL_CORR_SLAB; e += 256) {
+        const int r = e / VNL_CORR_SLAB, k = e % VNL_CORR_SLAB, row = row0 + r, c = s0 + k;
+        xs[h][r * VNL_CORR_LD + k] = row < R && c < c1 ? corr_row_value(vs, reward, scale, T, B, row, c) - mean[row] : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int k = 0; k < VNL_CORR_SLAB; k++) {
+      float va[4], vb[4];
+#pragma unroll
+      for (int a = 0; a < 4; a++) va[a] = xi[(ty + 16 * a) * VNL_CORR_LD + k], vb[a] = xj[(tx + 16 * a) * VNL_CORR_LD + k];
+#pragma unroll
+      for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) acc[a][b] = fmaf(va[a], vb[b], acc[a][b]);
+    }
+    __syncthreads();
+  }
+  float* P = part + (size_t)chunk * R * R;
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const int i = ti * VNL_CORR_TILE + ty + 16 * a, j = tj * VNL_CORR_TILE + tx + 16 * b;
+      if (i < R && j < R) {
+        P[(size_t)i * R + j] = acc[a][b];
+        if (ti != tj) P[(size_t)j * R + i] = acc[a][b];
+      }
+    }
+}
+
+// (One workgroup walks chunks x R^2 partial sums: sized for R = 2T in the tens to low hundreds -- unroll lengths of PPO, 40 at
+// the reference's -- where it is a few microseconds.  It stays correct for any R the plan accepts, but from R in the
+// thousands on it is a serial tail on the value stream; a finish split over row blocks would be the step then.)
+// entry `e` of the partial matrices, added in ascending chunk order; eight loads in flight at a time (one load per trip made
+// every chunk a memory round trip: 29 us for the finish at 32 chunks against 9.8 us, profiles/prediction_corr_bench.txt)
+__device__ __forceinline__ float corr_sum_chunks(const float* part, int chunks, size_t RR, size_t e) {
+  float d = 0.f;
+  int c = 0;
+  for (; c + 8 <= chunks; c += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = part[(c + u) * RR + e];
+#pragma unroll
+    for (int u = 0; u < 8; u++) d += v[u];
+  }
+  for (; c < chunks; c++) d += part[c * RR + e];
+  return d;
+}
+
+__global__ void __launch_bounds__(VNL_CORR_THREADS) prediction_corr_finish_kernel(const float* part, int chunks, int R, float* nrm2,
+                                                                                  float* out) {
+  __shared__ float red[VNL_CORR_THREADS];
+  const int tid = threadIdx.x;
+  const size_t RR = (size_t)R * R;
+  for (int i = tid; i < R; i += VNL_CORR_THREADS) {
+    nrm2[i] = corr_sum_chunks(part, chunks, RR, (size_t)i * R + i);
+  }
+  __syncthreads();  // (nrm2 is read by this workgroup only)
+  float acc = 0.f;
+  for (size_t pq = tid; pq < RR; pq += VNL_CORR_THREADS) {
+    const int i = (int)(pq / R), j = (int)(pq - (size_t)i * R);
+    const float d = corr_sum_chunks(part, chunks, RR, pq);
+    const float v = d / (sqrtf(nrm2[i]) * sqrtf(nrm2[j]));
+    acc += v != v ? v : fminf(fmaxf(v, -1.f), 1.f);
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int k = VNL_CORR_THREADS / 2; k > 0; k >>= 1) {
+    if (tid < k) red[tid] += red[tid + k];
+    __syncthreads();
+  }
+  if (tid == 0) *out = red[0] / (float)RR;
+}
+
+// Route rule and the tiled route's split, from (T, B) alone: route 1 (prediction_corr_kernel, one workgroup) wherever its
+// rows fit in 60 KB of LDS, so those sizes keep their bits; route 2 elsewhere.  At most VNL_CORR_MAX_CHUNKS partial
+// matrices (fewer when R is large: the workspace stays below 16 MB until one R x R matrix alone exceeds that); a workgroup
+// loops over the slabs of its chunk.
+static int corr_plan_(int T, int B, int route_request, vnl_corr_plan* p) {
+  const size_t R = (size_t)2 * T;
+  const bool fits = (R * (size_t)B + R) * sizeof(float) <= 60 * 1024;
+  if (route_request == 1 && !fits) return pfail(VNL_ERR_ARG, "prediction_corr: the rows do not fit the one-workgroup route's LDS");
+  p->route = route_request ? route_request : (fits ? 1 : 2);
+  p->chunks = 0, p->chunk_cols = 0, p->row_tiles = 0, p->workspace_floats = 0;
+  if (p->route == 1) return VNL_OK;
+  size_t cap = ((size_t)1 << 22) / (R * R);
+  cap = cap < 1 ? 1 : cap > VNL_CORR_MAX_CHUNKS ? VNL_CORR_MAX_CHUNKS : cap;
+  const size_t per = ((size_t)B + cap - 1) / cap;
+  p->chunk_cols = (int32_t)((per + VNL_CORR_SLAB - 1) / VNL_CORR_SLAB * VNL_CORR_SLAB);
+  p->chunks = (B + p->chunk_cols - 1) / p->chunk_cols;
+  p->row_tiles = (int32_t)((R + VNL_CORR_TILE - 1) / VNL_CORR_TILE);
+  p->workspace_floats = (int64_t)(2 * R + (size_t)p->chunks * R * R);
+  return VNL_OK;
+}
+
+static int prediction_corr_(const float* vs, const float* reward, float scale, int T, int B, int route_request, float* ws,
+                            int64_t ws_floats, float* out, hipStream_t st) {
+  vnl_corr_plan p;
+  const int rc = corr_plan_(T, B, route_request, &p);
+  if (rc != VNL_OK) return rc;
+  if (p.route == 1) {
+    const size_t lds = ((size_t)2 * T * B + 2 * T) * sizeof(float);
+    hipLaunchKernelGGL(prediction_corr_kernel, dim3(1), dim3(VNL_CORR_THREADS), lds, st, vs, reward, scale, T, B, out);
+    return VNL_OK;
+  }
+  if (!ws || ws_floats < p.workspace_floats) return pfail(VNL_ERR_ARG, "prediction_corr: workspace missing or too small (vnl_prediction_corr_plan)");
+  const int R = 2 * T;
+  float *mean = ws, *nrm2 = ws + R, *part = ws + 2 * (size_t)R;
+  hipLaunchKernelGGL(prediction_corr_mean_kernel, dim3(R), dim3(256), 0, st, vs, reward, scale, T, B, mean);
+  hipLaunchKernelGGL(prediction_corr_gram_kernel, dim3(p.row_tiles * (p.row_tiles + 1) / 2, p.chunks), dim3(256), 0, st, vs, reward, scale,
+                     T, B, p.chunk_cols, (const float*)mean, part);
+  hipLaunchKernelGGL(prediction_corr_finish_kernel, dim3(1), dim3(VNL_CORR_THREADS), 0, st, (const float*)part, p.chunks, R, nrm2, out);
+  return VNL_OK;
+}
+
+static int corr_args_(int32_t T, int32_t B, int32_t route_request) {
+  if (T < 1 || B < 2) return pfail(VNL_ERR_ARG, "prediction_corr: T must be >= 1 and B >= 2");
+  if (T > (1 << 29)) return pfail(VNL_ERR_ARG, "prediction_corr: T too large");
+  if (route_request < 0 || route_request > 2) return pfail(VNL_ERR_ARG, "prediction_corr: route_request must be 0, 1 or 2");
+  return VNL_OK;
+}
+
+extern "C" int vnl_prediction_corr_plan(int32_t T, int32_t B, int32_t route_request, vnl_corr_plan* out) {
+  if (!out) return pfail(VNL_ERR_ARG, "vnl_prediction_corr_plan: null argument");
+  const int rc = corr_args_(T, B, route_request);
+  return rc != VNL_OK ? rc : corr_plan_(T, B, route_request, out);
+}
+
+extern "C" int vnl_prediction_corr(const float* vs, const float* reward, float reward_scaling, int32_t T, int32_t B, int32_t route_request,
+                                   float* workspace, int64_t workspace_floats, float* out, void* stream) {
+  if (!vs || !reward || !out) return pfail(VNL_ERR_ARG, "vnl_prediction_corr: null argument");
+  int rc = corr_args_(T, B, route_request);
+  if (rc != VNL_OK) return rc;
+  if ((int64_t)T * B > INT32_MAX) return pfail(VNL_ERR_ARG, "vnl_prediction_corr: T * B must fit 32 bits");
+  rc = prediction_corr_(vs, reward, reward_scaling, T, B, route_request, workspace, workspace_floats, out, (hipStream_t)stream);
+  if (rc != VNL_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? pfail(VNL_ERR_HIP, hipGetErrorString(e)) : VNL_OK;
+}
+
 __global__ void __launch_bounds__(256) split_ml_kernel(const float* ml, float* mean, float* logvar, int N, int lat) {
   __builtin_amdgcn_s_setprio(3);
   const size_t n = (size_t)N * lat;
@@ -773,6 +959,8 @@ struct vnl_ppo_update {
   float *obsn = nullptr, *trajp = nullptr, *D0 = nullptr, *ml = nullptr, *mean = nullptr, *logvar = nullptr, *logits = nullptr;
   float *v = nullptr, *gl = nullptr, *gb = nullptr, *gklm = nullptr, *gkll = nullptr, *vs = nullptr, *adv = nullptr, *headws = nullptr;
   float *dml = nullptr, *dA = nullptr, *dB = nullptr, *dPa = nullptr, *dPb = nullptr, *slabs = nullptr, *part = nullptr;
+  float* corrws = nullptr;   // prediction_corr's tiled route: row means, squared norms, partial Gram matrices (corr_plan_)
+  int64_t corrws_floats = 0;
   float* dzarena = nullptr;  // d loss / d (pre-activations) of every LayerNorm layer: each keeps its own buffer until the
                              // step's grouped weight-gradient launch has read it
   size_t dz_floats = 0;
@@ -919,6 +1107,12 @@ extern "C" int vnl_ppo_update_create(const vnl_ppo_net_spec* sp, int32_t T, int3
   AL(u->vs, N);
   AL(u->adv, N);
   AL(u->headws, VNL_PPO_HEAD_WORKSPACE_FLOATS);
+  {
+    vnl_corr_plan cp;
+    (void)corr_plan_(T, B, 0, &cp);
+    u->corrws_floats = cp.workspace_floats;
+    if (cp.route == 2) AL(u->corrws, (size_t)cp.workspace_floats);
+  }
   AL(u->dml, N * 2 * sp->latent_size);
   AL(u->dA, Nv * wmax);
   AL(u->dB, Nv * wmax);
@@ -1182,14 +1376,10 @@ extern "C" int vnl_ppo_minibatch_grad_part(vnl_ppo_update* u, const float* param
       int rc = vnl_ppo_head_phase_(&a, u->headws, stream, 1);
       if (rc != VNL_OK) return rc;
       PCHK(hipEventRecord(u->ev[2], st));
-      // metrics[8] = prediction_corr (a metric only), in the same slack; NaN ("not computed", never a fake 0.0) when the 2T
-      // rows do not fit in LDS -- the same rule as the torch backend (intention_losses.py: _corr_fits)
-      const size_t lds = ((size_t)2 * u->T * u->B + 2 * u->T) * sizeof(float);
-      if (lds <= 60 * 1024)
-        hipLaunchKernelGGL(prediction_corr_kernel, dim3(1), dim3(VNL_CORR_THREADS), lds, st, (const float*)u->vs, bt->reward, hp->reward_scaling,
-                           u->T, u->B, metrics + 8);
-      else
-        PCHK(hipMemsetAsync(metrics + 8, 0xff, sizeof(float), st));  // 0xffffffff: a quiet NaN
+      // metrics[8] = prediction_corr (a metric only), in the same slack: one workgroup where the 2T rows fit in LDS, the
+      // tiled route (three launches, workspace sized in create) elsewhere
+      rc = prediction_corr_(u->vs, bt->reward, hp->reward_scaling, u->T, u->B, 0, u->corrws, u->corrws_floats, metrics + 8, st);
+      if (rc != VNL_OK) return rc;
       // the per-sample head (policy / entropy / KL terms, d loss / d logits, d loss / d latent heads) on the intention
       // network's stream, right behind its forward pass and in front of its backward pass
       PCHK(hipStreamWaitEvent(sp2, u->ev[2], 0));

@@ -29,6 +29,39 @@ def supported(ppo_network) -> bool:
     return pol.decoder_layers[-1] == 2 * dist.event_size
 
 
+def prediction_corr_plan(T: int, B: int, route: int = 0) -> "_lib.CorrPlan":
+    """vnl_prediction_corr_plan: the route (1 one workgroup, 2 tiled) and the tiled route's split for a [T, B] minibatch."""
+    lib = _lib.load_library()
+    plan = _lib.CorrPlan()
+    _lib.check(lib, lib.vnl_prediction_corr_plan(T, B, route, C.byref(plan)))
+    return plan
+
+
+def prediction_corr(vs: torch.Tensor, reward: torch.Tensor, scaling: float, route: int = 0,
+                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """metrics["prediction_corr"] on its own (vnl_prediction_corr): the mean of corrcoef([vs ; reward * scaling]) for
+    time-major float32 [T, B] tensors on a HIP device.  `route`: 0 = what the update step takes, 1 / 2 = force the
+    one-workgroup / the tiled kernels.  `out` [1] and `workspace` (prediction_corr_plan(...).workspace_floats floats) may be
+    passed in, so that a captured call allocates nothing."""
+    if vs.device.type != "cuda" or vs.dtype != torch.float32 or reward.dtype != torch.float32 or vs.shape != reward.shape \
+            or vs.dim() != 2:
+        raise _lib.VnlError("prediction_corr: float32 [T, B] tensors on a HIP device; no CPU fallback")
+    lib = _lib.load_library()
+    T, B = vs.shape
+    plan = prediction_corr_plan(T, B, route)
+    vs, reward = vs.contiguous(), reward.contiguous()
+    if workspace is None:
+        workspace = torch.empty(max(int(plan.workspace_floats), 1), dtype=torch.float32, device=vs.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=vs.device)
+    stream = C.c_void_p(torch.cuda.current_stream(vs.device).cuda_stream)
+    with torch.cuda.device(vs.device):
+        _lib.check(lib, lib.vnl_prediction_corr(C.c_void_p(vs.data_ptr()), C.c_void_p(reward.data_ptr()), float(scaling), T, B,
+                                                route, C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                                C.c_void_p(out.data_ptr()), stream))
+    return out
+
+
 class HipPPOUpdate:
     def __init__(self, ppo_network, T: int, B: int, device, *, entropy_cost, discounting, reward_scaling, gae_lambda,
                  clipping_epsilon, normalize_advantage, kl_weight):
