@@ -19,6 +19,9 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          balanced blocked form, EnvWave::blk_apply: same sums in another order)
 #   tail   -DVNL_SOLVER_TAIL: the solver's last permitted iteration computes its gradient / M^-1 grad / search update
 #          although nothing reads them (regression build for the skipped tail of EnvWave::solve: the same bits on every output)
+#   plain  -DVNL_SOLVER_PLAIN: the solver loop as it was before its per-lane constants were staged -- index tables and friction
+#          read from global memory, a block-descriptor load per product (regression build and bisecting tool for the staged
+#          form, EnvWaveT::with_solve_regs / load_tables: the same values from another place, the same bits on every output)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -31,6 +34,7 @@ VARIANTS = {
     "spill": ("libvnl_spill.so", ["-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(4,4)))"]),
     "noblk": ("libvnl_noblk.so", ["-DVNL_NO_BLK", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "tail": ("libvnl_tail.so", ["-DVNL_SOLVER_TAIL", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "plain": ("libvnl_plain.so", ["-DVNL_SOLVER_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

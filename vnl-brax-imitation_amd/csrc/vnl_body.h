@@ -242,6 +242,23 @@ VNL_HD S6 mcross_force(S6 v, S6 f) { return S6{cross(v.a, f.a) + cross(v.l, f.l)
 // from the constant block, VnlSpecRodent has them as constants)
 #define MI(f) (SP::fixed ? SP::D.f : m.f)
 #define LO(f) (SP::fixed ? SP::L.f : L.f)
+// Per-lane constants of the solve phase held in REGISTERS (device code; the host simulation reads the tables where they are,
+// and so does the regression build -DVNL_SOLVER_PLAIN, csrc/build.py --plain: today's form of everything the solver loop used
+// to fetch from global memory -- same values, so the same bits on every output)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_SOLVER_PLAIN)
+#define VNL_SOLVE_REGS 1
+#else
+#define VNL_SOLVE_REGS 0
+#endif
+#define VNL_BLK_REGS 2 /* trips of each form of blk_apply whose descriptors a lane keeps (the rodent: 2 + 2; further trips load theirs) */
+#define VNL_LIMROW_REGS 2 /* dofs per lane whose dof_limrow word a lane keeps: nv <= 128 (beyond: read where it is used) */
+#define VNL_SR_BLK 1    /* VnlSolveRegs::on: the block descriptors are loaded */
+#define VNL_SR_LIMROW 2 /* .. and the dof_limrow words */
+struct VnlSolveRegs {
+  int on;                            // wave-uniform: VNL_SR_* bits, which of the registers below are loaded
+  unsigned blk[2][VNL_BLK_REGS];     // [row form | column form][trip]: this lane's block descriptor
+  int limrow[VNL_LIMROW_REGS];       // m.dof_limrow[lane + 64 q]
+};
 template <class SP>
 struct EnvWaveT {
   const VNL_CAS DevModel& m;
@@ -252,14 +269,52 @@ struct EnvWaveT {
   unsigned e, lane;
   const VNL_CAS KernelConsts* kc;
   int* trace;  // debug only (vnl_env_debug): VNL_TRACE_INTS ints for the solver call of the current forward pass, or null
+  VnlSolveRegs sr;  // (zero where the kernel builds its view: nothing held)
   // The same view with the constant block's address made opaque to the optimiser: constants read by the stage that
   // follows are loaded there (scalar loads) instead of being kept alive -- spilled to VGPR lanes and fetched back
   // with v_readlane -- from the top of the kernel.
-  VNL_HD EnvWaveT with_trace(int* t) const { return EnvWaveT{m, ev, st, L, s, e, lane, kc, t}; }
+  VNL_HD EnvWaveT with_trace(int* t) const { return EnvWaveT{m, ev, st, L, s, e, lane, kc, t, sr}; }
   VNL_HD EnvWaveT fresh() const {
     const VNL_CAS KernelConsts* k = kc;
     VNL_LAUNDER(k);
-    return EnvWaveT{k->m, k->ev, st, k->L, s, e, lane, k, trace};
+    return EnvWaveT{k->m, k->ev, st, k->L, s, e, lane, k, trace, sr};
+  }
+  // The view whose solve-phase registers are loaded: the block descriptors of blk_apply (1 KB as a table, for which LDS has
+  // no room) and, with_limrow, the dof_limrow words of constraint_force.  ONE exposed vector-memory round trip, requested
+  // where a phase begins (forward() before smooth_forces, euler() before its product) instead of one per product and per
+  // constraint_force(); the empty asm pins the values there -- the compiler otherwise sinks every load to its use.
+  VNL_HD EnvWaveT with_solve_regs(bool with_limrow) const {
+    EnvWaveT w = *this;
+#if VNL_SOLVE_REGS
+    const int cfg = MI(blk_cfg), tr = cfg & 15, tc = (cfg >> 4) & 15;
+    const bool blk = blk_on();
+#pragma unroll
+    for (int t = 0; t < VNL_BLK_REGS; t++) {
+      w.sr.blk[0][t] = (blk && t < tr) ? m.blk_tab[t * 64 + (int)lane] : 0u;
+      w.sr.blk[1][t] = (blk && t < tc) ? m.blk_tab[(tr + t) * 64 + (int)lane] : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < VNL_LIMROW_REGS; q++) {
+      const int d = (int)lane + 64 * q;
+      w.sr.limrow[q] = (with_limrow && d < MI(nv)) ? m.dof_limrow[d] : 0;
+    }
+#pragma unroll
+    for (int t = 0; t < VNL_BLK_REGS; t++) asm volatile("" : "+v"(w.sr.blk[0][t]), "+v"(w.sr.blk[1][t]));
+    if (with_limrow) {
+#pragma unroll
+      for (int q = 0; q < VNL_LIMROW_REGS; q++) asm volatile("" : "+v"(w.sr.limrow[q]));
+    }
+    w.sr.on = with_limrow ? (VNL_SR_BLK | VNL_SR_LIMROW) : VNL_SR_BLK;
+#endif
+    return w;
+  }
+  // dof_limrow[d] of the dof this lane visits in a VNL_FOR(d, nv) trip
+  VNL_HD int limrow_of(int d) const {
+#if VNL_SOLVE_REGS
+    static_assert(VNL_LIMROW_REGS == 2, "limrow_of selects between exactly two registers");
+    if ((sr.on & VNL_SR_LIMROW) && d < 64 * VNL_LIMROW_REGS) return d < 64 ? sr.limrow[0] : sr.limrow[1];
+#endif
+    return m.dof_limrow[d];
   }
 #ifdef VNL_PROFILE
   VNL_HD void prof_begin() const {
@@ -386,6 +441,20 @@ struct EnvWaveT {
   // dofs sorted by depth: lvl_dof(q) for q in [lvl_start(l), lvl_start(l+1)) are the dofs of depth l
   VNL_HD int lvl_dof(int q) const { return ((const unsigned char*)(s + LO(tab_lvl)))[q]; }
   VNL_HD int lvl_start(int l) const { return ((const unsigned char*)(s + LO(tab_lvl)))[MI(nv) + l]; }
+  // the solver loop's per-contact / per-row lookups: staged in LDS by load_tables (friction: by make_constraint, per substep)
+#ifndef VNL_SOLVER_PLAIN
+  VNL_HD int con_geom_of(int c) const { return ((const unsigned char*)(s + LO(tab_con)))[2 * c]; }
+  VNL_HD int con_ordered(int k) const { return ((const unsigned char*)(s + LO(tab_con)))[2 * k + 1]; }  // the k-th contact in body order
+  VNL_HD int lim_dof_of(int r) const { return ((const unsigned char*)(s + LO(tab_lim)))[r]; }
+  VNL_HD int con_path_run(int c, int k) const { return ((const unsigned short*)(s + LO(tab_path)))[c * MI(path_runs) + k]; }
+  VNL_HD vreal con_mu_of(int g) const { return s[LO(con_mu) + g]; }
+#else
+  VNL_HD int con_geom_of(int c) const { return m.con_geom[c] & 0xff; }
+  VNL_HD int con_ordered(int k) const { return (m.con_geom[k] >> 8) & 0xff; }
+  VNL_HD int lim_dof_of(int r) const { return m.lim_dof[r]; }
+  VNL_HD int con_path_run(int c, int k) const { return m.body_pathseg[8 * con_body(c) + k]; }
+  VNL_HD vreal con_mu_of(int g) const { return par<P_MU>(g); }
+#endif
   VNL_HD int jump_of(int r, int b) const { return ((const unsigned char*)(s + LO(tab_jump)))[r * MI(nbody) + b]; }
   VNL_HD void load_tables() const {
     unsigned char* ta = (unsigned char*)(s + LO(tab_anc));
@@ -401,11 +470,19 @@ struct EnvWaveT {
       tb[MI(nbody) + b] = (unsigned char)m.body_dofadr[b];
       tb[2 * MI(nbody) + b] = (unsigned char)m.body_dofnum[b];
     }
+    unsigned char* tc = (unsigned char*)(s + LO(tab_con));
+    unsigned short* tp = (unsigned short*)(s + LO(tab_path));
     VNL_FOR(c, MI(ncon)) {
-      int cb = m.cg_body[m.con_geom[c] & 0xff];
+      const int cg = m.con_geom[c];
+      int cb = m.cg_body[cg & 0xff];
       tb[3 * MI(nbody) + c] = (unsigned char)cb;
       tb[3 * MI(nbody) + MI(ncon) + c] = (unsigned char)m.body_lastdof[cb];
+      tc[2 * c] = (unsigned char)(cg & 0xff), tc[2 * c + 1] = (unsigned char)((cg >> 8) & 0xff);
+      for (int k = 0; k < MI(path_runs); k++) tp[c * MI(path_runs) + k] = (unsigned short)m.body_pathseg[8 * cb + k];
     }
+    // (8-bit dofs, 16-bit runs of 8-bit dofs: nv <= 255 as for tab_body / tab_lvl -- vnl_lib.hip: build_dev_model rejects more)
+    unsigned char* tlim = (unsigned char*)(s + LO(tab_lim));
+    VNL_FOR(r, MI(nlimit)) tlim[r] = (unsigned char)m.lim_dof[r];
     unsigned char* tl = (unsigned char*)(s + LO(tab_lvl));
     VNL_FOR(q, MI(nv) + MI(max_depth) + 2) tl[q] = m.lvl_tab[q];
     unsigned char* tj = (unsigned char*)(s + LO(tab_jump));
@@ -1310,7 +1387,7 @@ struct EnvWaveT {
       VNL_PERLANE(unsigned, dsc);
       VNL_FOR(l, VNL_WAVE_ITEMS(64)) {
 #ifdef __HIP_DEVICE_COMPILE__
-        const unsigned d = pre[trip];
+        const unsigned d = (VNL_SOLVE_REGS && (sr.on & VNL_SR_BLK) && trip < VNL_BLK_REGS) ? sr.blk[COL ? 1 : 0][trip] : pre[trip];
 #else
         const unsigned d = tab[trip * 64 + l];
 #endif
@@ -1606,6 +1683,7 @@ struct EnvWaveT {
       }
       V3 t2 = cross(n, t1);
       vreal mu = par<P_MU>(g), margin = m.cg_margin[g], invw = par<P_INVW>(g);
+      s[LO(con_mu) + g] = mu;  // (for the solver loop: jac_mul, constraint_force)
       S6 vel = ld6(cvel + 6 * bd);
       for (int q = 0; q < nc; q++) {
         int c = c0 + q, r0 = MI(nlimit) + 4 * c;
@@ -1680,18 +1758,23 @@ struct EnvWaveT {
     }
     VNL_SYNC();
   }
-  // sum over the (at most 4) runs of consecutive dofs on a body's path: Q[end] - Q[begin] each
-  VNL_HD S6 path_sum(int Q, const int* seg) const {
+  // sum over the (at most 4) runs of consecutive dofs on a body's path: Q[end] - Q[begin] each; run(k) = begin | end << 8
+  // (ONE summation order for every caller: the plain and the staged builds agree bit for bit because of it)
+  template <class RUN>
+  VNL_HD S6 path_sum_runs(int Q, RUN run) const {
     S6 acc = S6{v3(0, 0, 0), v3(0, 0, 0)};
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       if (k >= MI(path_runs)) break;  // (no body of this model has more runs: two for the rodent)
-      const int sg = seg[k], b = sg & 0xff, e = sg >> 8;  // (an unused run is 0 | 0 << 8: Q[0] - Q[0])
+      const int sg = run(k), b = sg & 0xff, e = sg >> 8;  // (an unused run is 0 | 0 << 8: Q[0] - Q[0])
       S6 qe = ld6(Q + 6 * e), qb = ld6(Q + 6 * b);
       acc = S6{acc.a + (qe.a - qb.a), acc.l + (qe.l - qb.l)};
     }
     return acc;
   }
+  VNL_HD S6 path_sum(int Q, const int* seg) const { return path_sum_runs(Q, [&](int k) { return seg[k]; }); }
+  // .. of contact c's body, the runs read from their LDS table
+  VNL_HD S6 path_sum_con(int Q, int c) const { return path_sum_runs(Q, [&](int k) { return con_path_run(c, k); }); }
 
   // out[r] = (J vec)[r]  (accumulate: out[r] += ...).  Limit rows: one lane each.  Contact rows: the twist of
   // a contact's body is the sum of cdof_d * vec_d over the dofs d on the body's path; those dofs are a few runs of
@@ -1701,7 +1784,7 @@ struct EnvWaveT {
     V3 n = v3(m.pnx, m.pny, m.pnz);
     for_live_rows([&](int r) {
       if (r < MI(nlimit)) {
-        vreal v = copysign(vreal(1.), s[LO(efc_D) + r]) * s[vec + m.lim_dof[r]];
+        vreal v = copysign(vreal(1.), s[LO(efc_D) + r]) * s[vec + lim_dof_of(r)];
         s[out + r] = accumulate ? s[out + r] + v : v;
       }
     });
@@ -1710,10 +1793,9 @@ struct EnvWaveT {
     const unsigned char* act = (const unsigned char*)(s + LO(act_list));
     int na = ((const int*)(s + LO(act_list)))[(MI(ncon) + 3) / 4];
     VNL_FOR(j, na) {
-      int c = act[j], g = m.con_geom[c] & 0xff, r0 = MI(nlimit) + 4 * c;
-      const int* seg = m.body_pathseg + 8 * con_body(c);
-      S6 vel = path_sum(Q, seg);
-      vreal mu = par<P_MU>(g);
+      int c = act[j], g = con_geom_of(c), r0 = MI(nlimit) + 4 * c;
+      S6 vel = path_sum_con(Q, c);
+      vreal mu = con_mu_of(g);
       V3 rel = ld3(LO(con_r) + 3 * c), t1 = ld3(LO(con_t1) + 3 * g), t2 = cross(n, t1);
       V3 pv = vel.l + cross(vel.a, rel);
       vreal jn = dot(n, pv), j1 = dot(t1, pv) * mu, j2 = dot(t2, pv) * mu;
@@ -1758,12 +1840,12 @@ struct EnvWaveT {
       VNL_FOR(k, VNL_WAVE_ITEMS(MI(ncon))) {  // (ncon <= 64: one trip of ALL lanes; idle lanes carry zeros through the scan)
         S6 w = S6{v3(0, 0, 0), v3(0, 0, 0)};
         if (k < MI(ncon)) {
-          const int c = (m.con_geom[k] >> 8) & 0xff;  // the k-th contact in body order
+          const int c = con_ordered(k);  // the k-th contact in body order
           int r0 = MI(nlimit) + 4 * c;
           vreal D = s[LO(efc_D) + r0];
           if (D != vreal(0.)) {
-            int g = m.con_geom[c] & 0xff;
-            vreal mu = par<P_MU>(g), f[4];
+            int g = con_geom_of(c);
+            vreal mu = con_mu_of(g), f[4];
             for (int q = 0; q < 4; q++) {
               vreal x = s[LO(Jaref) + r0 + q];
               f[q] = x < vreal(0.) ? -D * x : vreal(0.);
@@ -1781,7 +1863,7 @@ struct EnvWaveT {
       }
       VNL_SYNC();
       VNL_FOR(d, MI(nv)) {
-        const int pk = m.dof_limrow[d], r = (pk & 0x3ff) - 1, c0 = (pk >> 10) & 0xff, c1 = (pk >> 18) & 0xff;
+        const int pk = limrow_of(d), r = (pk & 0x3ff) - 1, c0 = (pk >> 10) & 0xff, c1 = (pk >> 18) & 0xff;
         S6 p1 = ld6(Wc + 6 * c1), p0 = ld6(Wc + 6 * c0);
         S6 w = S6{p1.a - p0.a, p1.l - p0.l};
         vreal q = dot(ld6(LO(cdof) + 6 * d), w);
@@ -2258,9 +2340,10 @@ struct EnvWaveT {
       fresh().invert_factor();
     }
     VNL_PROF(11);
-    fresh().smooth_forces();
+    const EnvWaveT w = fresh().with_solve_regs(true);  // (from here on: the factorisations above want every register)
+    w.smooth_forces();
     VNL_PROF(12);
-    fresh().make_constraint(cvel);
+    w.make_constraint(cvel);
     VNL_PROF(13);
 #ifdef VNL_STAGE_KNOBS
     for (int rep = 0; rep < m.dbg_count; rep++) {
@@ -2297,7 +2380,7 @@ struct EnvWaveT {
       }
     }
 #endif
-    fresh().solve();
+    w.solve();
   }
 
   // forward.euler + _advance; leaves qacc (warm start) in LO(qacc) and the new state in LO(qpos)/qvel/act
@@ -2314,7 +2397,7 @@ struct EnvWaveT {
       VNL_SYNC_GLOBAL();  // (written by invert_aba, one row per lane; read here element by element)
       VNL_FOR(k, n2) s[LO(P) + k] = g2[k];
       VNL_SYNC();
-      fresh().solve_inplace(LO(tmp), LO(P), LO(P) + MI(nM));
+      fresh().with_solve_regs(false).solve_inplace(LO(tmp), LO(P), LO(P) + MI(nM));
       VNL_PROF(27);
     } else if (MI(eulerdamp)) {
       fresh().body_inertias(false);
@@ -2322,7 +2405,7 @@ struct EnvWaveT {
       fresh().mass_matrix(m.dt);
       fresh().factor();
       fresh().invert_factor();
-      fresh().solve_inplace(LO(tmp));
+      fresh().with_solve_regs(false).solve_inplace(LO(tmp));
       VNL_PROF(27);
     }
     VNL_FOR(i, MI(nu)) {

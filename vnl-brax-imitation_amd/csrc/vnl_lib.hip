@@ -839,6 +839,8 @@ static void layout(vnl_env* env) {
   sec("tab_body", L.tab_body, L.tab_jump - L.tab_body), sec("tab_jump", L.tab_jump, L.tab_lvl - L.tab_jump);
   sec("tab_lvl", L.tab_lvl, L.act_list - L.tab_lvl);
   sec("act_list", L.act_list, vnl_words(4 * (long)((d.ncon + 3) / 4) + 8 + 2 * VNL_LIVE_MAX));
+  sec("tab_con", L.tab_con, L.tab_path - L.tab_con), sec("tab_path", L.tab_path, L.tab_lim - L.tab_path);
+  sec("tab_lim", L.tab_lim, L.con_mu - L.tab_lim), sec("con_mu", L.con_mu, d.ncg);
   if (d.solver_newton) {  // qM, and the Hessian's inverted L'DL factor and pivots, in the qLD layout
     sec("newton_qM", L.newt_M, d.nM), sec("newton_LD", L.newt_H, d.nM), sec("newton_LDiagInv", L.newt_H + d.nM, d.nv);
   }
@@ -849,6 +851,11 @@ static void layout(vnl_env* env) {
 
 static bool same_layout(const WsLayout& a, const WsLayout& b) { return memcmp(&a, &b, sizeof(WsLayout)) == 0; }
 static bool same_dims(const VnlDims& a, const VnlDims& b) { return memcmp(&a, &b, sizeof(VnlDims)) == 0; }
+// eight workgroups per CU on 160 KB of LDS: the float32 rodent's working set, the solver's staged tables included, stays within 20,480 B
+// (the diagnostic build -DVNL_PROFILE adds 328 B of stage stamps and runs at seven: its shares are read, not its times)
+#ifndef VNL_PROFILE
+static_assert(sizeof(vreal) != 4 || (size_t)VnlSpecRodent::L.total * sizeof(vreal) <= 20480, "the rodent's LDS layout no longer allows 8 workgroups per CU");
+#endif
 
 #include "vnl_env_kernels.h"
 

@@ -133,6 +133,11 @@ struct WsLayout {
   int con_r, con_t1;    /* 3 per contact / 3 per collidable geom */
   int tab_anc, tab_madr, tab_body, tab_jump, tab_lvl; /* 8/16-bit index tables staged in LDS */
   int act_list;         /* ncon bytes: contacts with D != 0, then their count (int) */
+  /* what the solver loop looks up per lane, staged so that no iteration goes to global memory for it (EnvWaveT::load_tables,
+     make_constraint): per contact its geom | the contact at its place in body order (8 bits each); per contact the runs of
+     consecutive dofs on its body's path (path_runs x begin | end << 8, 16 bits each); per limit row its dof (8 bits); per
+     collidable geom the friction coefficient of this substep (this env's, in a randomised instantiation) */
+  int tab_con, tab_path, tab_lim, con_mu;
   int newt_M, newt_H; /* Newton solver only: qM in the qLD layout (nM), the Hessian's inverted L'DL factor in that layout (nM)
                          followed by its reciprocal pivots (nv) */
   int total;
@@ -182,6 +187,8 @@ constexpr WsLayout vnl_make_layout(const VnlDims& d) {
   L.tab_jump = sec(vnl_words((long)(d.jump_rounds > 0 ? d.jump_rounds : 1) * d.nbody));
   L.tab_lvl = sec(vnl_words((long)d.nv + d.max_depth + 2));
   L.act_list = sec(vnl_words(4 * (long)((d.ncon + 3) / 4) + 8 + 2 * VNL_LIVE_MAX)); /* active contacts | their count | existing rows: count, list */
+  L.tab_con = sec(vnl_words(2 * (long)d.ncon)), L.tab_path = sec(vnl_words(2 * (long)d.path_runs * d.ncon));
+  L.tab_lim = sec(vnl_words(d.nlimit)), L.con_mu = sec(d.ncg);
   L.newt_M = L.newt_H = 0;
   if (d.solver_newton) L.newt_M = sec(d.nM), L.newt_H = sec(d.nM + d.nv);
   if (VNL_NPROF_SLOTS) {
