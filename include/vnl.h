@@ -164,6 +164,48 @@ int vnl_env_dims(const vnl_env*, vnl_dims* out);
  * noise [num_envs][nq] (already scaled by reset_noise_scale; rodent.py:131-147). */
 int vnl_env_reset(vnl_env*, const int32_t* start_frame, const float* noise, const vnl_state* state, void* stream);
 
+/* A fresh episode for the envs whose mask word is nonzero, drawn INSIDE the kernel (the opt-in alternative to the auto-reset
+ * wrapper's cached first state): a new start frame, clip and reset noise per env and episode, from stream 3 of the
+ * counter layout of vnl_policy_noise below (streams 0..2 are the acting kernel's; the stream field is the low two bits of
+ * counter word 3, so 3 is the last one):
+ *   key     = (seed low 32 bits, seed high 32 bits)
+ *   counter = (block, env_offset + e, step low 32 bits, (step >> 32) << 2 | 3),   step = *step_base + step_offset
+ *   blocks 0 .. (nq + 3) / 4 - 1: the reset noise, Box-Muller as for the policy's normals, times noise_scale; element j of the
+ *                                 row is output j % 4 of block j / 4
+ *   block 0x80000000            : start_frame = (x0 * start_hi) >> 32, clip_id = (x1 * num_clips) >> 32 (64-bit products; a
+ *                                 value's probability is off 1 / n by less than 2^-32)
+ * An env's draws depend on (seed, step, env_offset + e) alone: not on the mask, the batch size or the sharding.
+ * ppo_imitation/philox.py (reset_draws) restates them in torch ops.  The draws are stored -- into the record rows below, or
+ * into scratch of the library's when a record pointer is null -- and the reset body of vnl_env_reset runs on the stored rows:
+ * vnl_env_reset given the recorded start_frame, clip_id and noise returns the same bits.
+ * Written for a reset env: the pipeline state (qpos .. qfrc_actuator), obs, traj, termination_error, cur_frame,
+ * sub_clip_frame (0) and clip_id.  NOT written: reward, done and metrics, which keep the terminal step's values as under
+ * brax's auto-reset.  Nothing of an env whose mask is 0 is touched; per-env domain tables stay as they are.
+ * Then, for EVERY env, each of the `num_logs` (0..8) log descriptors copies row src[e][width] to log[e][width] (32-bit
+ * words, as vnl_rollout_post moves rows): next_observation and the logged info fields of a rollout record the post-reset
+ * values without a launch of their own.
+ * The kernel only READS the step counter; the caller advances it in stream order (see vnl_policy_noise).  VNL_ERR_ARG, with
+ * nothing launched, for a null mask / descriptor / state / step_base, start_hi < 1, a negative offset, env_offset +
+ * num_envs >= 2^32 - 1, or num_logs outside 0..8.  With vnl_env_debug on, the image and trace row 0 of reset envs are written. */
+typedef struct vnl_reset_noise {
+  uint64_t seed;
+  const int64_t* step_base; /* device, [1], read only */
+  int64_t step_offset;      /* host value, >= 0 */
+  int64_t env_offset;       /* global index of env 0, >= 0 */
+  int32_t start_hi;         /* start_frame uniform in [0, start_hi) */
+  float noise_scale;        /* rodent.py:31 reset_noise_scale */
+  int32_t* start_frame_out; /* optional records, [num_envs] / [num_envs] / [num_envs][nq] (the env's real type, as the noise of */
+  int32_t* clip_id_out;     /* vnl_env_reset): only the rows of reset envs are written */
+  float* noise_out;
+} vnl_reset_noise;
+typedef struct vnl_reset_log {
+  const float* src;
+  float* log;
+  int32_t width, pad_;
+} vnl_reset_log;
+int vnl_env_reset_done(vnl_env*, const float* mask /* [num_envs] float32 */, const vnl_reset_noise*, const vnl_state*,
+                       const vnl_reset_log* logs, int32_t num_logs, void* stream);
+
 /* step: action [num_envs][nu]; state updated in place. */
 int vnl_env_step(vnl_env*, const float* action, const vnl_state* state, void* stream);
 /* Forward kinematics only (reference preprocessing/mjx_preprocess.py:85-107: `mjx.kinematics` scanned over the frames of a

@@ -1,0 +1,135 @@
+"""Fresh starts on auto-reset on the device: vnl_reset_done_kernel in its four instantiations (specialised rodent, generic, and
+the per-env-table forms of both), the captured unroll in fresh mode against the eager one, and a short train() run."""
+import functools
+
+import pytest
+import torch
+
+import body_domain_cases as BD
+import domain_cases as D
+import fresh_reset_cases as F
+import helpers as H
+from vnl_brax_imitation_amd.envs.rodent import RodentTracking
+from vnl_brax_imitation_amd.envs.wrappers import AutoResetWrapper, EpisodeWrapper
+from vnl_brax_imitation_amd.ppo_imitation import acting, ppo_networks, running_statistics
+from vnl_brax_imitation_amd.ppo_imitation import train as ppo
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+DOM_TABLES = ("dom_mu", "dom_invw", "dom_gain", "dom_damp", "dom_arm", "dom_mass", "dom_ipos", "dom_inertia6", "dom_tminv")
+
+
+def _masks(B):
+    """roughly one env in three, from a fixed generator"""
+    g = torch.Generator().manual_seed(17)
+    return (torch.rand(B, generator=g) < 1 / 3).float(), (torch.rand(B, generator=g) < 1 / 3).float()
+
+
+def _rodent(B, clip=None):
+    return RodentTracking(clip if clip is not None else F.three_clips(), num_envs=B, device=DEV, **H.env_kwargs())
+
+
+def test_specialised_rodent_kernel_256_envs():
+    """Items 1-3 of tests/test_fresh_reset.py at 256 envs (more than one workgroup per CU slot), three clips."""
+    env = _rodent(256)
+    assert env.dims.kernel_specialised == 1
+    F.check_items_1_to_3(env, *_masks(256))
+
+
+def test_generic_kernel_64_envs():
+    from test_generic_model import _ant_env
+
+    env = _ant_env(64, "float", device="cuda:0")
+    assert env.dims.kernel_specialised == 0
+    F.check_items_1_to_3(env, *_masks(64))
+
+
+@pytest.mark.parametrize("model", ["rodent", "ant"])
+def test_randomised_env_keeps_its_tables_64_envs(model):
+    """The VnlSpecDom instantiations, a four-field and a body domain set: the reset is vnl_env_reset of the SAME randomised
+    env, and the per-env tables are bit-identical before and after."""
+    if model == "rodent":
+        base = _rodent(64)
+    else:
+        from test_generic_model import _ant_env
+
+        base = _ant_env(64, "float", device="cuda:0")
+    env = base.with_domain(D.random_domain(base.sys, 64, 21)).with_body_domain(BD.random_body_domain(base.sys, 64, 22))
+    tables = {k: env.domain_table(k) for k in DOM_TABLES}
+    F.check_items_1_to_3(env, *_masks(64))
+    for k, v in tables.items():
+        assert torch.equal(env.domain_table(k), v), k
+
+
+def _setup(mode, B=64, episode_length=150):
+    base = _rodent(B, H.reference_clip())  # the reference's sub_clip_length = 10: episodes end inside a 12-step unroll
+    env = AutoResetWrapper(EpisodeWrapper(base, episode_length=episode_length, action_repeat=1), mode=mode, seed=41)
+    nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
+                                                    preprocess_observations_fn=running_statistics.normalize,
+                                                    intention_latent_size=16, encoder_layer_sizes=(32,),
+                                                    decoder_layer_sizes=(32,))
+    flat = nets.policy_network.init(torch.Generator().manual_seed(0)).to(DEV)
+    norm = running_statistics.init_state(base.observation_size, device=DEV)
+    policy = ppo_networks.make_inference_fn(nets)((norm, flat), noise="device", seed=9)
+    return env, policy, env.reset(torch.Generator().manual_seed(5))
+
+
+def _state_leaves(s, mode):
+    return [s.obs, s.done, s.reward] + [s.pipeline_state.raw(n) for n in s.pipeline_state._FIELDS] + \
+        [s.info[k] for k in ("steps", "truncation", "traj", "cur_frame", "sub_clip_frame", "clip_id")] + \
+        ([s.info["reset_step"]] if mode == "fresh" else [])
+
+
+@pytest.mark.parametrize("mode,replays", [("fresh", 2), ("first_state", 1)])
+def test_captured_unroll_equals_the_eager_unroll_bit_for_bit(mode, replays):
+    """After test_graphed_unroll_equals_the_eager_unroll_bit_for_bit: device-noise policy, B = 64, T = 12; in fresh mode two
+    replays (the counter's hand-over between them), in the default mode one (the default path with the new code present)."""
+    T, extra = 12, ("truncation", "traj")
+    runs = []
+    for graphed in (False, True):
+        env, policy, state = _setup(mode)
+        first_frames = state.info["cur_frame"].clone()
+        g = acting.GraphedUnroll(env, state, policy, None, T, extra_fields=extra) if graphed else None
+        if mode == "fresh":
+            assert int(state.info["reset_step"]) == 0  # building the graph draws nothing
+        datas = []
+        for _ in range(replays):
+            state, data = g() if g else acting.generate_unroll(env, state, policy, None, T, extra_fields=extra, fused=True)
+            datas.append([x.clone() for x in acting._leaves(data)])
+        torch.cuda.synchronize(DEV)
+        if mode == "fresh":
+            assert int(state.info["reset_step"]) == T * replays
+            # every env finished its 10-frame sub-clip inside the first unroll and went on from a DRAWN frame
+            assert float((1 - data.discount).sum()) > 0
+            assert not torch.equal(state.info["cur_frame"] - state.info["sub_clip_frame"], first_frames)
+        runs.append((datas, [x.clone() for x in _state_leaves(state, mode)]))
+    (d0, s0), (d1, s1) = runs
+    for a_, b_ in zip(d0, d1):
+        for a, b in zip(a_, b_):
+            assert a.shape == b.shape and torch.equal(a, b)
+    for a, b in zip(s0, s1):
+        assert torch.equal(a, b)
+
+
+def test_train_with_fresh_resets():
+    """One train() call with auto_reset="fresh" at the smallest sizes of tests/test_gpu_train.py, two training steps."""
+    env = RodentTracking(H.reference_clip(), num_envs=64, device=DEV, **H.env_kwargs())
+    nf = functools.partial(ppo_networks.make_intention_ppo_networks, intention_latent_size=60,
+                           encoder_layer_sizes=(128, 128), decoder_layer_sizes=(128, 128))
+    seed, log = 3, []
+    first = env.reset(torch.Generator().manual_seed(seed * 1000003 + 17)).info["cur_frame"].clone()  # train()'s first reset
+    _, (norm, flat), _ = ppo.train(
+        environment=env, num_timesteps=2 * 64 * 5, episode_length=150, num_envs=64, learning_rate=1e-3,
+        entropy_cost=1e-2, discounting=0.95, unroll_length=5, batch_size=16, num_minibatches=4,
+        num_updates_per_batch=2, num_evals=1, normalize_observations=True, network_factory=nf, num_eval_envs=0,
+        eval_env=None, seed=seed, policy_noise="device", auto_reset="fresh", progress_fn=lambda s, m: log.append(m))
+    st = ppo.train.last_env_state
+    assert all(torch.isfinite(torch.as_tensor(float(v))) for v in log[-1].values())
+    assert torch.isfinite(flat).all()
+    init = ppo.train.last_ppo_network.policy_network.init(torch.Generator().manual_seed(seed))  # train()'s first draw
+    assert init.shape == flat.shape and not torch.equal(flat.cpu(), init)  # parameters changed
+    assert int(st.info["reset_step"]) == 10
+    # ten control steps of 10-frame sub-clips: every env has just started its second episode, at a drawn frame
+    start = (st.info["cur_frame"] - st.info["sub_clip_frame"]).cpu()
+    assert sorted(start.tolist()) != sorted(first.cpu().tolist())
+    assert bool(((start >= 0) & (start < 235)).all())

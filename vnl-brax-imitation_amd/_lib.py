@@ -86,6 +86,19 @@ class PolicyNoise(C.Structure):  # include/vnl.h: vnl_policy_noise
                 ("eps_latent_out", C.c_void_p), ("eps_action_out", C.c_void_p), ("rand_action_out", C.c_void_p)]
 
 
+class ResetNoise(C.Structure):  # include/vnl.h: vnl_reset_noise
+    _fields_ = [("seed", C.c_uint64), ("step_base", C.c_void_p), ("step_offset", C.c_int64), ("env_offset", C.c_int64),
+                ("start_hi", C.c_int32), ("noise_scale", C.c_float),
+                ("start_frame_out", C.c_void_p), ("clip_id_out", C.c_void_p), ("noise_out", C.c_void_p)]
+
+
+RESET_MAX_LOGS = 8
+
+
+class ResetLog(C.Structure):  # include/vnl.h: vnl_reset_log
+    _fields_ = [("src", C.c_void_p), ("log", C.c_void_p), ("width", C.c_int32), ("pad_", C.c_int32)]
+
+
 POST_MAX_OPS = 24
 
 
@@ -153,7 +166,7 @@ class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device
 
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
-    "vnl_env_dims", "vnl_env_reset", "vnl_env_step", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
+    "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_step", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
     "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
@@ -180,6 +193,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.vnl_env_destroy.restype = None
     lib.vnl_env_dims.argtypes = [vp, C.POINTER(Dims)]
     lib.vnl_env_reset.argtypes = [vp, vp, vp, C.POINTER(StatePtrs), vp]
+    lib.vnl_env_reset_done.argtypes = [vp, vp, C.POINTER(ResetNoise), C.POINTER(StatePtrs), C.POINTER(ResetLog), C.c_int32, vp]
     lib.vnl_env_step.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     lib.vnl_env_fk.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     lib.vnl_env_debug.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]

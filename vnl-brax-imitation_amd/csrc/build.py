@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # (vnl_domain.hip last: the randomised env kernels, a translation unit of their own -- vnl_env_set_domain -- listed after the
 # existing kernels in the resource report)
 SOURCES = ["vnl_lib.hip", "vnl_policy.hip", "vnl_ppo.hip", "vnl_domain.hip"]
-DEPS = SOURCES + ["vnl_env_kernels.h", "vnl_body.h", "vnl_types.h", "vnl_policy_train.h", "../../include/vnl.h"]
+DEPS = SOURCES + ["vnl_env_kernels.h", "vnl_body.h", "vnl_types.h", "vnl_philox.h", "vnl_policy_train.h", "../../include/vnl.h"]
 OUT = os.path.join(HERE, "libvnl.so")
 
 # Diagnostic / regression builds of the SAME sources (never the product library, only loaded by tools/ and tests/):
@@ -38,7 +38,7 @@ VARIANTS = {
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }
-ENV_KERNELS = ("vnl_step_kernel", "vnl_reset_kernel")
+ENV_KERNELS = ("vnl_step_kernel", "vnl_reset_kernel", "vnl_reset_done_kernel")
 
 
 def resource_usage(stderr_text: str) -> dict:
@@ -77,7 +77,7 @@ def build(force: bool = False, verbose: bool = False, profile: bool = False, kno
         defs + os.environ.get("VNL_HIPCC_EXTRA", "").split()
     stamp = " ".join(flags)
     headers = [d for d in deps if not d.endswith(".hip")]
-    SRC_DEPS = {"vnl_lib.hip": headers, "vnl_policy.hip": [h for h in headers if h.endswith("vnl.h")] + [os.path.join(HERE, "vnl_policy_train.h")],
+    SRC_DEPS = {"vnl_lib.hip": headers, "vnl_policy.hip": [h for h in headers if h.endswith("vnl.h")] + [os.path.join(HERE, "vnl_policy_train.h"), os.path.join(HERE, "vnl_philox.h")],
                 "vnl_ppo.hip": [h for h in headers if h.endswith("vnl.h")] + [os.path.join(HERE, "vnl_policy_train.h")]}
     objs, remarks = [], ""
     for src in SOURCES:

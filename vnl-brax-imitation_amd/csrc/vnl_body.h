@@ -36,6 +36,7 @@
 #ifndef VNL_HD
 #define VNL_HD __device__ __forceinline__
 #endif
+#include "vnl_philox.h"
 
 // ---- fork-join primitives (the host simulation in tests/hostsim redefines them) ------------
 #ifndef VNL_FORKJOIN_DEFINED
@@ -2580,7 +2581,10 @@ struct EnvWaveT {
     VNL_FOR(k, 4) st.qpos[(size_t)e * MI(nq) + 3 + k] = s[LO(qpos) + 3 + k];  // the root quaternion as kinematics normalised it
   }
 
-  VNL_HD void reset(const int* start_frame, const vreal* noise, int* trace_base) const {
+  // KEEP_TERMINAL (the fresh reset of a finished env, reset_fresh): reward, done and the metrics keep the terminal step's
+  // values, as under brax's auto-reset; everything else is written as by vnl_env_reset
+  template <bool KEEP_TERMINAL>
+  VNL_HD void reset_core(const int* start_frame, const vreal* noise, int* trace_base) const {
     load_tables();
     int clip = st.clip_id[e], sf = start_frame[e];
     int f = clampi(sf, 0, ev.T - 1), nj = MI(nq) - 7;
@@ -2602,11 +2606,50 @@ struct EnvWaveT {
     write_obs();
     vreal term = termination(clip, sf, s + LO(qpos), gxpos());
     VNL_SERIAL {
-      st.reward[e] = vreal(0.), st.done[e] = vreal(0.);
-      for (int k = 0; k < 7; k++) st.metrics[(size_t)e * 7 + k] = vreal(0.);
+      if (!KEEP_TERMINAL) {
+        st.reward[e] = vreal(0.), st.done[e] = vreal(0.);
+        for (int k = 0; k < 7; k++) st.metrics[(size_t)e * 7 + k] = vreal(0.);
+      }
       st.cur_frame[e] = sf, st.sub_clip_frame[e] = 0;
       st.term_err[e] = term;
     }
+  }
+  VNL_HD void reset(const int* start_frame, const vreal* noise, int* trace_base) const {
+    reset_core<false>(start_frame, noise, trace_base);
+  }
+
+  // A new episode for THIS env, drawn here (include/vnl.h: vnl_env_reset_done): stream 3 of the counter layout the acting
+  // kernel's noise uses (streams 0..2), keyed by (seed, step, global env index) -- the draws depend on neither the batch
+  // size nor the sharding nor on which other envs reset.  Blocks 0 .. (nq + 3) / 4 - 1 give the reset noise (Box-Muller as
+  // draw_normal_tile maps words to normals, times noise_scale; element j = output j % 4 of block j / 4), block 0x80000000
+  // the integers by multiply-shift: start_frame = (x0 * start_hi) >> 32, clip_id = (x1 * num_clips) >> 32.  The shift maps
+  // floor or ceil of 2^32 / n words to each value, so a value's probability is off 1 / n by less than 2^-32: a relative
+  // bias under 2^-32 * start_hi (5.5e-8 for the reference's 235 start frames).
+  // The draws go through memory -- the caller's record rows or library scratch -- and the reset body of vnl_env_reset then
+  // runs on those rows: the arithmetic of a fresh reset IS that of vnl_env_reset given the recorded draws.
+  VNL_HD void reset_fresh(const ResetDoneArgs& a, int* trace_base) const {
+    const int nq = MI(nq), nblk = (nq + 3) >> 2;
+    const int64_t step = *a.step_base + a.step_offset;
+    const uint32_t c1 = a.env0 + (uint32_t)e, c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
+    vreal* nz = a.noise + (size_t)e * nq;
+    VNL_FOR(b, nblk) {
+      uint32_t x[4];
+      philox4x32_10((uint32_t)b, c1, c2, c3, a.key0, a.key1, x);
+      float v[4];
+      box_muller(x[0], x[1], v[0], v[1]);
+      box_muller(x[2], x[3], v[2], v[3]);
+      for (int q = 0; q < 4; q++)
+        if (4 * b + q < nq) nz[4 * b + q] = vreal(v[q] * a.noise_scale);
+    }
+    VNL_SERIAL {
+      uint32_t x[4];
+      philox4x32_10(0x80000000u, c1, c2, c3, a.key0, a.key1, x);
+      const int clip = (int)(((uint64_t)x[1] * (uint32_t)ev.C) >> 32);
+      a.start_frame[e] = (int)(((uint64_t)x[0] * a.start_hi) >> 32);
+      a.clip_id[e] = clip, st.clip_id[e] = clip;
+    }
+    VNL_SYNC_GLOBAL();  // (every lane reads the start frame and clip that lane 0 stored, and the noise row)
+    reset_core<true>(a.start_frame, a.noise, trace_base);
   }
 
   // _calculate_reward (rodent.py:266-316 / humanoid.py:264-311) on a pipeline state given by pointers, against the clip

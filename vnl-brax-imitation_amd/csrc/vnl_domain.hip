@@ -33,3 +33,14 @@ int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* 
                        action, dump, dump_mid, trace);
   return (int)hipGetLastError();
 }
+
+int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds,
+                           const ResetDoneArgs& a, vreal* dump, int* trace) {
+  if (spec)
+    hipLaunchKernelGGL((vnl_reset_done_kernel<VnlSpecDom<VnlSpecRodent>>), dim3(B), dim3(64), lds, (hipStream_t)stream, kc, ds, a,
+                       dump, trace);
+  else
+    hipLaunchKernelGGL((vnl_reset_done_kernel<VnlSpecDom<VnlSpecGeneric>>), dim3(B), dim3(64), lds, (hipStream_t)stream, kc, ds, a,
+                       dump, trace);
+  return (int)hipGetLastError();
+}

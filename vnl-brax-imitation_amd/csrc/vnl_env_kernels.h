@@ -34,3 +34,25 @@ __global__ void VNL_ENV_KERNEL vnl_reset_kernel(const KernelConsts* kc, DevState
   if (dump) w.dump(dump);
 }
 
+
+// A fresh episode for the envs whose mask is set (EnvWaveT::reset_fresh), then up to VNL_RESET_MAX_LOGS row copies for EVERY
+// env (32-bit words, as vnl_rollout_post moves rows: next_observation[t] and the logged state extras record the post-reset
+// values without a launch of their own).  An env that does not reset reads its mask word and goes straight to the copies:
+// no tables, no LDS.
+template <class SP>
+__global__ void VNL_ENV_KERNEL vnl_reset_done_kernel(const KernelConsts* kc, DevState st, ResetDoneArgs a, vreal* dump, int* trace) {
+  VNL_LDS_DECL(lds);
+  const unsigned e = blockIdx.x, lane = threadIdx.x;
+  if (a.mask[e] != 0.f) {
+    const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
+    EnvWaveT<SP> w{k->m, k->ev, st, k->L, lds, e, lane, k, nullptr};
+    w.reset_fresh(a, trace);
+    if (dump) w.dump(dump);
+    VNL_SYNC_GLOBAL();  // (the copies below read rows that other lanes stored)
+  }
+  for (int q = 0; q < a.num_logs; q++) {
+    const unsigned* src = a.logs[q].src + (size_t)e * a.logs[q].width;
+    unsigned* log = a.logs[q].log + (size_t)e * a.logs[q].width;
+    VNL_FOR(i, a.logs[q].width) log[i] = src[i];
+  }
+}

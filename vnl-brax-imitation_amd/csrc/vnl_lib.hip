@@ -107,6 +107,9 @@ struct vnl_env {
   KernelConsts* kc = nullptr;  // device copy of {dm, de, L}
   vreal* dump = nullptr;  // [B][L.total] image of the per-env LDS, written only when debug is on
   int* trace = nullptr;   // [B][n_frames][VNL_TRACE_INTS] solver decisions, written only when debug is on
+  // vnl_env_reset_done: where the draws of a fresh reset go when the caller asks for no record ([B] | [B] | [B][nq])
+  int *rd_start = nullptr, *rd_clip = nullptr;
+  vreal* rd_noise = nullptr;
   int debug = 0;          // 0 off, 1 image at the end of reset / step, 2 image after the last forward pass of a step
   int spec = 0;           // 1: the kernels specialised for the rodent's dims and layout (VnlSpecRodent) run this env
   size_t lds_bytes = 0;
@@ -933,6 +936,13 @@ extern "C" int vnl_env_create(const vnl_model* hm, const vnl_envspec* es, int32_
     env->allocs.push_back(p);
     e.fac2 = (vreal*)p;
   }
+  {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, (size_t)num_envs * (2 * sizeof(int) + d.nq * sizeof(vreal))));
+    env->allocs.push_back(p);
+    env->rd_noise = (vreal*)p;
+    env->rd_start = (int*)(env->rd_noise + (size_t)num_envs * d.nq), env->rd_clip = env->rd_start + num_envs;
+  }
   layout(env);
   // a model whose every dimension and LDS offset equals the compile-time constants of a specialised kernel runs that kernel
   env->spec = (same_dims(dims_of(env->dm), VnlSpecRodent::D) && same_layout(env->L, VnlSpecRodent::L)) ? 1 : 0;
@@ -1045,7 +1055,7 @@ extern "C" int vnl_env_debug(vnl_env* env, int32_t enable, int32_t* row_stride) 
 }
 
 // ----------------------------------------------------------------------------- kernels
-// (vnl_step_kernel / vnl_reset_kernel: vnl_env_kernels.h)
+// (vnl_step_kernel / vnl_reset_kernel / vnl_reset_done_kernel: vnl_env_kernels.h)
 __global__ void __launch_bounds__(64) vnl_fk_kernel(const KernelConsts* kc, DevState st, const vreal* qpos) {
   VNL_LDS_DECL(lds);
   const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
@@ -1058,6 +1068,8 @@ int vnl_domain_reset_(const KernelConsts* kc, int spec, int B, size_t lds, void*
                       const vreal* noise, vreal* dump, int* trace);
 int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const vreal* action,
                      vreal* dump, vreal* dump_mid, int* trace);
+int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds,
+                           const ResetDoneArgs& a, vreal* dump, int* trace);
 
 static int to_dev_state(const vnl_state* s, DevState* d) {
   const void* ptrs[] = {s->qpos, s->qvel, s->act, s->qacc_warmstart, s->xpos, s->xquat, s->subtree_com1,
@@ -1096,6 +1108,50 @@ extern "C" int vnl_env_reset(vnl_env* env, const int32_t* start_frame, const flo
     hipLaunchKernelGGL((vnl_reset_kernel<VnlSpecGeneric>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
                        (const KernelConsts*)env->kc, ds, (const int*)start_frame, (const vreal*)noise,
                        env->debug ? env->dump : nullptr, env->debug ? env->trace : nullptr);
+  HIPCHK(hipGetLastError());
+  return VNL_OK;
+}
+
+// A fresh episode, drawn in the kernel, for the envs whose mask is set (include/vnl.h; EnvWaveT::reset_fresh)
+extern "C" int vnl_env_reset_done(vnl_env* env, const float* mask, const vnl_reset_noise* noise, const vnl_state* state,
+                                  const vnl_reset_log* logs, int32_t num_logs, void* stream) {
+  if (!env || !mask || !noise || !state) return fail(VNL_ERR_ARG, "vnl_env_reset_done: null argument");
+  if (!noise->step_base) return fail(VNL_ERR_ARG, "vnl_reset_noise: step_base is null (a device pointer to the step counter)");
+  if (noise->start_hi < 1) return fail(VNL_ERR_ARG, "vnl_reset_noise: start_hi must be at least 1");
+  if (noise->step_offset < 0 || noise->env_offset < 0)
+    return fail(VNL_ERR_ARG, "vnl_reset_noise: step_offset and env_offset must not be negative");
+  if (noise->env_offset >= 0xFFFFFFFFll - (int64_t)env->B)  // (no sum: an offset near INT64_MAX must not wrap)
+    return fail(VNL_ERR_ARG, "vnl_reset_noise: env_offset + num_envs must stay below 2^32 - 1");
+  if (num_logs < 0 || num_logs > VNL_RESET_MAX_LOGS || (num_logs > 0 && !logs))
+    return fail(VNL_ERR_ARG, "vnl_env_reset_done: num_logs must be 0..8, with logs given");
+  for (int k = 0; k < num_logs; k++)
+    if (!logs[k].src || !logs[k].log || logs[k].width <= 0) return fail(VNL_ERR_ARG, "vnl_env_reset_done: bad log");
+  DevState ds;
+  int rc = to_dev_state(state, &ds);
+  if (rc != VNL_OK) return rc;
+  ResetDoneArgs a{};
+  a.mask = mask, a.step_base = noise->step_base, a.step_offset = noise->step_offset;
+  a.key0 = (uint32_t)noise->seed, a.key1 = (uint32_t)(noise->seed >> 32), a.env0 = (uint32_t)noise->env_offset;
+  a.start_hi = (uint32_t)noise->start_hi, a.noise_scale = noise->noise_scale, a.num_logs = num_logs;
+  a.start_frame = noise->start_frame_out ? (int*)noise->start_frame_out : env->rd_start;
+  a.clip_id = noise->clip_id_out ? (int*)noise->clip_id_out : env->rd_clip;
+  a.noise = noise->noise_out ? (vreal*)noise->noise_out : env->rd_noise;
+  for (int k = 0; k < num_logs; k++)
+    a.logs[k].src = (const unsigned*)logs[k].src, a.logs[k].log = (unsigned*)logs[k].log, a.logs[k].width = logs[k].width;
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+  vreal* dump = env->debug ? env->dump : nullptr;
+  int* trace = env->debug ? env->trace : nullptr;
+  if (env->has_dom) {
+    HIPCHK((hipError_t)vnl_domain_reset_done_(env->kc, env->spec, env->B, env->lds_bytes, stream, ds, a, dump, trace));
+    return VNL_OK;
+  }
+  if (env->spec)
+    hipLaunchKernelGGL((vnl_reset_done_kernel<VnlSpecRodent>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
+                       (const KernelConsts*)env->kc, ds, a, dump, trace);
+  else
+    hipLaunchKernelGGL((vnl_reset_done_kernel<VnlSpecGeneric>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
+                       (const KernelConsts*)env->kc, ds, a, dump, trace);
   HIPCHK(hipGetLastError());
   return VNL_OK;
 }

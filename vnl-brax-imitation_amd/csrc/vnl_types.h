@@ -118,6 +118,27 @@ struct DevState {
   int *cur_frame, *sub_clip_frame, *clip_id;
 };
 
+// arguments of vnl_reset_done_kernel, by value (include/vnl.h: vnl_env_reset_done, vnl_reset_noise, vnl_reset_log)
+#define VNL_RESET_MAX_LOGS 8
+struct ResetDoneArgs {
+  const float* mask;        /* [num_envs], nonzero = reset this env */
+  const int64_t* step_base; /* device, [1], read only */
+  int64_t step_offset;
+  uint32_t key0, key1;      /* seed low | high */
+  uint32_t env0;            /* global index of env 0 */
+  uint32_t start_hi;        /* start_frame uniform in [0, start_hi) */
+  float noise_scale;
+  int num_logs;
+  /* the draws, written by the kernel and then read by the reset body (the caller's records or library-owned scratch) */
+  int *start_frame, *clip_id;
+  vreal* noise; /* [num_envs][nq] */
+  struct {
+    const unsigned* src;
+    unsigned* log;
+    int width, pad_;
+  } logs[VNL_RESET_MAX_LOGS]; /* rows [num_envs][width] of 32-bit words */
+};
+
 // per-env LDS sections (offsets in vreal elements)
 struct WsLayout {
   int qpos, qvel, act, ctrl, actdot, com;

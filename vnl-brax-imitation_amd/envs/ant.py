@@ -105,6 +105,17 @@ class AntTracking(RodentTracking):
             noise = torch.zeros((B, nq), dtype=torch.float32)
         return self._present(super().reset(rng, start_frame=start_frame, noise=noise, clip_id=clip_id, out=out))
 
+    def _start_hi(self) -> int:
+        return 1  # ant.py:90-171: every episode starts at frame 0
+
+    def reset_done(self, state: State, mask, *, logs=(), **kw) -> State:
+        """The fresh reset of RodentTracking.reset_done (frame 0, no noise, a new clip), then the assembled observation;
+        the logs are copied after that, so that a logged obs is the presented one."""
+        self._present(super().reset_done(state, mask, **kw))
+        for src, log in logs:
+            log.copy_(src)
+        return state
+
     def step(self, state: State, action: torch.Tensor) -> State:
         """ant.py:172-226."""
         return self._present(super().step(state, action))

@@ -66,6 +66,10 @@ class HumanoidTracking(RodentTracking):
             reference_clip = _pp.ReferenceClip.load(path) if path and os.path.exists(path) else standing_clip(m, clip_length)
         self._build(reference_clip, num_envs, device)
 
+    def _start_hi(self) -> int:
+        """humanoid.py:79-100: the episode, not a sub-clip, has to fit behind the start frame"""
+        return max(self._clip_length - self._episode_length - self._ref_traj_length, 1)
+
     def reset(self, rng=None, *, start_frame=None, noise=None, clip_id=None, out=None):
         """humanoid.py:79-133: start_frame ~ U[0, clip_length - episode_length - ref_traj_length), no noise."""
         B, nq = self.num_envs, int(self.dims.nq)

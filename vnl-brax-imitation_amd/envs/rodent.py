@@ -409,6 +409,52 @@ class RodentTracking(Env):
         self._hold = (sf, nz)  # keep inputs alive until the stream has consumed them
         return state
 
+    def _start_hi(self) -> int:
+        """Start frames of this env's own `reset` are uniform in [0, _start_hi()) (rodent.py:123-128); at least 1."""
+        return max(self._clip_length - self._sub_clip_length - self._ref_traj_length, 1)
+
+    def reset_done(self, state: State, mask: torch.Tensor, *, seed: int, step_base: torch.Tensor, step_offset: int = 0,
+                   env_offset: int = 0, logs=(), record: Optional[Dict[str, torch.Tensor]] = None) -> State:
+        """A fresh episode, in place, for the envs whose `mask` (B,) is nonzero (vnl_env_reset_done): start frame in
+        [0, _start_hi()) -- the range of this env's own `reset` --, clip and reset noise drawn in the kernel from the counter-based
+        stream keyed by (seed, step_base[0] + step_offset, env_offset + env index) -- ppo_imitation/philox.py reset_draws.
+        reward, done and metrics keep the terminal step's values; nothing of an unmasked env changes.  `step_base`: int64 [1]
+        on the env's device, only read (the caller advances it).  `logs`: up to 8 (src, log) pairs of (B[, w]) float32 /
+        int32 tensors, log <- src for every env after the reset.  `record`: optional dict of int32 (B,) "start_frame",
+        "clip_id" and (B, nq) "noise" tensors that receive the draws of the reset envs."""
+        B = self.num_envs
+        if tuple(mask.shape) != (B,):
+            raise ValueError(f"mask must be ({B},), got {tuple(mask.shape)}")
+        if step_base.dtype != torch.int64 or step_base.numel() != 1 or step_base.device != self.device:
+            raise ValueError("step_base must be an int64 tensor of one element on the env's device")
+        mk = mask.to(device=self.device, dtype=torch.float32).contiguous()
+        nz = _lib.ResetNoise()
+        nz.seed, nz.step_base = int(seed) & 0xFFFFFFFFFFFFFFFF, step_base.data_ptr()
+        nz.step_offset, nz.env_offset = int(step_offset), int(env_offset)
+        nz.start_hi = self._start_hi()
+        nz.noise_scale = self._reset_noise_scale
+        record = record or {}
+        for k, dt in (("start_frame", torch.int32), ("clip_id", torch.int32), ("noise", self._dtype)):
+            t = record.get(k)
+            if t is not None:
+                if t.dtype != dt or not t.is_contiguous() or t.shape[0] != B or t.device != self.device:
+                    raise ValueError(f"record[{k!r}] must be a contiguous {dt} tensor with {B} rows on the env's device")
+                setattr(nz, k + "_out", t.data_ptr())
+        logs = tuple(logs)
+        if len(logs) > _lib.RESET_MAX_LOGS:
+            raise ValueError(f"at most {_lib.RESET_MAX_LOGS} logs")
+        arr = (_lib.ResetLog * max(len(logs), 1))()
+        for o, (src, log) in zip(arr, logs):
+            if src.dtype not in (torch.float32, torch.int32) or log.dtype != src.dtype or src.shape != log.shape or \
+                    src.shape[0] != B or not (src.is_contiguous() and log.is_contiguous()):
+                raise ValueError("a log is a (src, log) pair of contiguous float32 / int32 tensors of one shape (B[, w])")
+            o.src, o.log, o.width = src.data_ptr(), log.data_ptr(), src.numel() // B
+        p = self._ptrs(state)
+        _lib.check(self._L, self._L.vnl_env_reset_done(self._env_h, mk.data_ptr(), C.byref(nz), C.byref(p), arr, len(logs),
+                                                       self._stream()))
+        self._hold = (mk, step_base, logs, record)  # keep inputs alive until the stream has consumed them
+        return state
+
     def step(self, state: State, action: torch.Tensor) -> State:
         """rodent.py:178-239.  action: (B, nu)."""
         nu, B = int(self.dims.nu), self.num_envs

@@ -75,19 +75,39 @@ class EpisodeWrapper(Wrapper):
         return state
 
 
-class AutoResetWrapper(Wrapper):
-    """Automatically resets done envs to the cached first state (brax AutoResetWrapper).
+AUTO_RESET_MODES = ("first_state", "fresh")
 
-    As in brax, only `pipeline_state` and `obs` are restored; `info` (cur_frame,
-    sub_clip_frame, traj) is NOT unless reset_info_on_autoreset=True.
+
+class AutoResetWrapper(Wrapper):
+    """Automatically resets done envs.
+
+    mode="first_state" (default; brax AutoResetWrapper): to the cached first state.  As in brax, only `pipeline_state` and
+    `obs` are restored; `info` (cur_frame, sub_clip_frame, traj) is NOT unless
+    reset_info_on_autoreset=True.
+
+    mode="fresh": to a NEW episode -- start frame, clip and reset noise drawn on the device per env and episode
+    (`env.reset_done`, vnl_env_reset_done), keyed by (seed, info["reset_step"], env_offset + env index): no first state is
+    cached, and the whole of `info` follows the reset.  `info["reset_step"]` is an int64[1] device counter that advances by
+    one per step.  reward / done / metrics of the terminal step are kept, as under brax's auto-reset.
     """
 
-    def __init__(self, env: Env, reset_info_on_autoreset: bool = False):
+    def __init__(self, env: Env, reset_info_on_autoreset: bool = False, mode: str = "first_state", seed: int = 0,
+                 env_offset: int = 0):
         super().__init__(env)
+        if mode not in AUTO_RESET_MODES:
+            raise ValueError(f"unknown auto-reset mode {mode!r}: expected one of {AUTO_RESET_MODES}")
+        if mode == "fresh" and reset_info_on_autoreset:
+            raise ValueError("reset_info_on_autoreset has no meaning with mode='fresh': a fresh reset rewrites the info")
+        if mode == "fresh" and not hasattr(env.unwrapped, "reset_done"):
+            raise ValueError(f"{type(env.unwrapped).__name__} has no reset_done: mode='fresh' needs a tracking env of this library")
         self.reset_info = reset_info_on_autoreset
+        self.mode, self.seed, self.env_offset = mode, int(seed), int(env_offset)
 
     def reset(self, rng=None, **kw) -> State:
         state = self.env.reset(rng, **kw)
+        if self.mode == "fresh":
+            state.info["reset_step"] = torch.zeros(1, dtype=torch.int64, device=state.obs.device)
+            return state
         state.info["first_pipeline_state"] = state.pipeline_state.clone()
         state.info["first_obs"] = state.obs.clone()
         if self.reset_info:
@@ -100,6 +120,11 @@ class AutoResetWrapper(Wrapper):
             steps.copy_(torch.where(state.done.bool(), torch.zeros_like(steps), steps))
         state.done.zero_()
         state = self.env.step(state, action)
+        if self.mode == "fresh":
+            counter = state.info["reset_step"]
+            self.env.unwrapped.reset_done(state, state.done, seed=self.seed, step_base=counter, env_offset=self.env_offset)
+            counter.add_(1)
+            return state
         done = state.done.bool()
         state.pipeline_state.copy_(state.info["first_pipeline_state"], mask=done)
         state.obs.copy_(torch.where(done[:, None], state.info["first_obs"], state.obs))
@@ -144,13 +169,18 @@ class EvalWrapper(Wrapper):
 
 
 def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None,
-         reset_info_on_autoreset: bool = False) -> Wrapper:
+         reset_info_on_autoreset: bool = False, auto_reset: str = "first_state", auto_reset_seed: int = 0,
+         env_offset: int = 0) -> Wrapper:
     """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
 
     `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
     num_envs and rng): its result goes to `env.with_domain` (cg_friction, act_gain, dof_damping, dof_armature) and, for the
     keys body_mass, body_inertia, body_ipos, to `env.with_body_domain`: a NEW env with per-env model parameters.  An unknown
-    key raises.  The caller's env is left as it is."""
+    key raises.  The caller's env is left as it is.
+
+    `auto_reset`: "first_state" (brax: a done env returns to the cached first state) or "fresh" (a new start frame, clip
+    and reset noise per episode, drawn on the device; AutoResetWrapper), with `auto_reset_seed` and `env_offset` (the global
+    index of this batch's env 0, for sharded runs) keying the draws."""
     if randomization_fn is not None:
         if not hasattr(env, "with_domain"):
             raise ValueError(f"{type(env).__name__} has no with_domain: domain randomisation needs a tracking env of this library")
@@ -162,4 +192,5 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
             env = env.with_domain(domain)
         if bodies:
             env = env.with_body_domain(bodies)
-    return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset)
+    return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset, mode=auto_reset,
+                            seed=auto_reset_seed, env_offset=env_offset)

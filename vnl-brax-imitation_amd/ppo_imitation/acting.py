@@ -71,7 +71,9 @@ _DIRECT_LOG = True
 
 def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int, extra_fields) -> Tuple[State, Transition]:
     """Same results as the generic loop below (tests compare the two), 2 launches per step besides the
-    policy: the env step kernel and vnl_rollout_post (which also writes the Transition's observation row).
+    policy: the env step kernel and vnl_rollout_post (which also writes the Transition's observation row).  With
+    AutoResetWrapper(mode="fresh") a third one, vnl_env_reset_done, starts the new episodes and writes the rows the reset
+    changes (next_observation, the logged info fields); its draws are keyed by info["reset_step"] + t.
 
     With a device-noise policy step t draws at `policy.counter + t` and the counter advances by T once, after the loop (one
     small launch per unroll instead of three noise launches per step; inside a captured graph the offsets are baked in and the
@@ -100,19 +102,25 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
                                                             ptr(info["truncation"]), ptr(st.reward))
     d.episode_length, d.action_repeat = ep.episode_length, 1
     ops = []  # (dst, src, first, log rows [T, B, w] or None)
-    fps = info["first_pipeline_state"]
-    for name in st.pipeline_state._FIELDS:
-        cur = st.pipeline_state.raw(name)
-        ops.append((cur, cur, fps.raw(name), None))
-    ops.append((st.obs, st.obs, info["first_obs"], nobs_log))
-    logged = set()
-    if ar.reset_info:
-        for k2, v in info["first_info"].items():
-            ops.append((info[k2], info[k2], v, sx_log.get(k2)))
-            logged.add(k2)
-    for x in extra_fields:
-        if x not in logged and x != "truncation":
-            ops.append((None, info[x], None, sx_log[x]))
+    fresh = getattr(ar, "mode", "first_state") == "fresh"
+    if fresh:
+        # a done env starts a NEW episode (vnl_env_reset_done after the post launch, mask = the finalised done): nothing is
+        # restored from a first state, and what the reset rewrites -- obs, the info fields -- is logged by that launch
+        reset_logs = [(st.obs, nobs_log)] + [(info[x], sx_log[x]) for x in extra_fields if x != "truncation"]
+    else:
+        fps = info["first_pipeline_state"]
+        for name in st.pipeline_state._FIELDS:
+            cur = st.pipeline_state.raw(name)
+            ops.append((cur, cur, fps.raw(name), None))
+        ops.append((st.obs, st.obs, info["first_obs"], nobs_log))
+        logged = set()
+        if ar.reset_info:
+            for k2, v in info["first_info"].items():
+                ops.append((info[k2], info[k2], v, sx_log.get(k2)))
+                logged.add(k2)
+        for x in extra_fields:
+            if x not in logged and x != "truncation":
+                ops.append((None, info[x], None, sx_log[x]))
     n_static = len(ops)
     px_log: Optional[dict] = None
     act_log = None
@@ -151,6 +159,11 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
         d.log_truncation = ptr(sx_log["truncation"][t]) if "truncation" in sx_log else C.c_void_p(0)
         _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
         _generate_unroll_fused.hold = keep  # the launch is asynchronous: keep this step's sources alive
+        if fresh:
+            base.reset_done(st, st.done, seed=ar.seed, step_base=info["reset_step"], step_offset=t, env_offset=ar.env_offset,
+                            logs=[(src, log[t]) for src, log in reset_logs])
+    if fresh:  # (like policy.counter: the launches carry offsets 0..T-1, one add per unroll -- a node of a captured graph)
+        info["reset_step"].add_(T)
     if dev_noise:
         policy.counter.add_(T)
     obs_log = torch.cat((obs0[None], nobs_log[:-1]), dim=0)
@@ -243,7 +256,9 @@ def generate_unroll(env, env_state: State, policy, key, unroll_length: int,
     buffers allocated once per call (the env mutates its State in place).
     NB (reference behaviour): state_extras['traj'] is nstate.info['traj'], i.e. the reference
     trajectory features AFTER the step (acting.py:49), not the ones the policy saw.
-    `fused` (default: whenever possible) routes the wrappers + logging through vnl_rollout_post."""
+    `fused` (default: whenever possible) routes the wrappers + logging through vnl_rollout_post.  With
+    AutoResetWrapper(mode="fresh") the fused route logs obs and every extra field but "truncation" through the 8 log slots
+    of vnl_env_reset_done: at most 7 such extra fields (ValueError beyond; `fused=False` has no such limit)."""
     fz = _fusable(env) if fused is not False else None
     if fused is True and fz is None:
         raise ValueError("fused rollout needs AutoResetWrapper(EpisodeWrapper(RodentTracking)), action_repeat 1")

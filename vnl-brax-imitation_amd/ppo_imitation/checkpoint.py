@@ -8,6 +8,7 @@ brax.io.model pickles the pytree).  Here the same pair goes to one `.npz` (NumPy
     policy/params/<flax path>            e.g. policy/params/encoder/hidden_0/kernel   (Dense kernels stay (in, out))
     [value/params/<flax path>, optimizer/{mu,nu,count}, meta/env_steps]   full training state, for resume
     [meta/policy_counter]                the acting policy's noise step counter (train(policy_noise="device"))
+    [meta/reset_step]                    the step counter of the fresh episode draws (train(auto_reset="fresh"))
 
 The tensor names are the reference's Flax tree (intention_policy_network.py:20-136), so a reference checkpoint
 converted to nested dicts of arrays maps 1:1 through `from_flax_tree` / `to_flax_tree`.
@@ -73,7 +74,8 @@ def _flatten(prefix: str, layout: ParamLayout, flat: torch.Tensor, out: Dict[str
 
 def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsState, torch.Tensor], ppo_network,
                 *, value_params: Optional[torch.Tensor] = None, optimizer_state: Optional[Dict[str, torch.Tensor]] = None,
-                env_steps: Optional[int] = None, policy_counter: Optional[torch.Tensor] = None) -> str:
+                env_steps: Optional[int] = None, policy_counter: Optional[torch.Tensor] = None,
+                reset_step: Optional[torch.Tensor] = None) -> str:
     """`params` = the inference pair the reference saves; the keyword extras make the file resumable."""
     norm, policy = params
     out: Dict[str, np.ndarray] = {f"normalizer/{k}": getattr(norm, k).detach().cpu().numpy() for k in _NORM}
@@ -87,6 +89,8 @@ def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsSta
         out["meta/env_steps"] = np.asarray(env_steps, dtype=np.int64)
     if policy_counter is not None:
         out["meta/policy_counter"] = policy_counter.detach().cpu().numpy().astype(np.int64).reshape(1)
+    if reset_step is not None:
+        out["meta/reset_step"] = reset_step.detach().cpu().numpy().astype(np.int64).reshape(1)
     if not path.endswith(".npz"):
         path += ".npz"
     np.savez(path, **out)
@@ -182,7 +186,7 @@ def convert_brax_params(pickle_path: str, ppo_network, npz_path: Optional[str] =
 
 
 def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
-    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps', 'policy_counter'}."""
+    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps', 'policy_counter', 'reset_step'}."""
     z = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
     t = lambda a: torch.from_numpy(np.asarray(a)).to(device) if device is not None else torch.from_numpy(np.asarray(a))  # noqa: E731
     norm = running_statistics.RunningStatisticsState(*(t(z[f"normalizer/{k}"]) for k in _NORM))
@@ -196,4 +200,6 @@ def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
         out["env_steps"] = int(z["meta/env_steps"])
     if "meta/policy_counter" in z.files:
         out["policy_counter"] = t(z["meta/policy_counter"])
+    if "meta/reset_step" in z.files:
+        out["reset_step"] = t(z["meta/reset_step"])
     return out

@@ -4,7 +4,9 @@
 
     key     = (seed low 32 bits, seed high 32 bits)
     counter = (block, env, step low 32 bits, (step >> 32) << 2 | stream),  step < 2^62
-    stream  = 0 latent draw, 1 action draw, 2 the random action shared by the batch (env = 0xFFFFFFFF)
+    stream  = 0 latent draw, 1 action draw, 2 the random action shared by the batch (env = 0xFFFFFFFF),
+              3 the fresh episode reset of an env (vnl_env_reset_done): blocks 0.. its reset noise, block 0x80000000 its
+              start frame and clip
 
 A call yields four words x0..x3; u_i = ((x_i >> 8) + 0.5) 2^-24 lies strictly inside (0, 1).  Normal draws are Box-Muller
 pairs, (u0, u1) -> sqrt(-2 ln u0) (cos, sin)(2 pi u1) and (u2, u3) likewise; element j of an env's row is output j % 4 of block
@@ -23,6 +25,8 @@ M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 MASK = 0xFFFFFFFF
 STREAM_LATENT, STREAM_ACTION, STREAM_SHARED = 0, 1, 2
+STREAM_RESET = 3  # the last one: the stream field is the low two bits of counter word 3
+RESET_INT_BLOCK = 0x80000000  # the block of stream 3 whose words x0, x1 give start frame and clip
 SHARED_ENV = 0xFFFFFFFF  # the env word of stream 2: no env may have this index
 
 IntLike = Union[int, torch.Tensor]
@@ -48,14 +52,14 @@ def philox4x32(counter: torch.Tensor, key: Tuple[IntLike, IntLike], rounds: int 
     return torch.stack((c0, c1, c2, c3), dim=-1)
 
 
-def _words(seed: int, step: IntLike, env: torch.Tensor, n: int, stream: int) -> torch.Tensor:
-    """The (n + 3) // 4 blocks of every env's row: int64 [len(env), blocks, 4].  `step` may be an int64 tensor on the
-    device (the policy's counter): nothing is read back to the host."""
+def _words(seed: int, step: IntLike, env: torch.Tensor, n: int, stream: int, block0: int = 0) -> torch.Tensor:
+    """The (n + 3) // 4 blocks of every env's row, from block `block0` on: int64 [len(env), blocks, 4].  `step` may be an
+    int64 tensor on the device (the policy's counter): nothing is read back to the host."""
     dev = env.device
     nb = (n + 3) // 4
     step = torch.as_tensor(step, dtype=torch.int64, device=dev).reshape(())
     shape = (env.shape[0], nb)
-    ctr = torch.stack((torch.arange(nb, dtype=torch.int64, device=dev).expand(shape),
+    ctr = torch.stack(((block0 + torch.arange(nb, dtype=torch.int64, device=dev)).expand(shape),
                        (env.to(torch.int64) & MASK)[:, None].expand(shape),
                        (step & MASK).expand(shape),
                        (((step >> 32) << 2) | stream).expand(shape)), dim=-1)
@@ -81,3 +85,21 @@ def shared_uniform(seed: int, step: IntLike, n: int, device=None) -> torch.Tenso
     env = torch.full((1,), SHARED_ENV, dtype=torch.int64, device=device)
     u = _unit(_words(seed, step, env, n, STREAM_SHARED))
     return (2.0 * u - 1.0).reshape(-1)[:n].to(torch.float32)
+
+
+def reset_draws(seed: int, step: IntLike, env: torch.Tensor, nq: int, start_hi: int, num_clips: int,
+                noise_scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(start_frame int64 [B], clip_id int64 [B], noise float32 [B, nq]) of a fresh reset (vnl_env_reset_done) of the envs
+    with GLOBAL indices `env` at `step`.  The integers are multiply-shift maps of words x0, x1 of block RESET_INT_BLOCK,
+    (x * n) >> 32, exact in int64 for n < 2^31 (x < 2^32)."""
+    x = _words(seed, step, env, 1, STREAM_RESET, block0=RESET_INT_BLOCK)[:, 0]  # [B, 4]
+    assert 0 < int(start_hi) < (1 << 31) and 0 < int(num_clips) < (1 << 31)
+
+    def below(w: torch.Tensor, n: int) -> torch.Tensor:
+        return (w * n) >> 32
+
+    u = _unit(_words(seed, step, env, nq, STREAM_RESET))
+    r = torch.sqrt(-2.0 * torch.log(u[..., 0::2]))
+    a = (2.0 * math.pi) * u[..., 1::2]
+    nz = torch.stack((r * torch.cos(a), r * torch.sin(a)), dim=-1).reshape(env.shape[0], -1)[:, :nq]
+    return below(x[:, 0], int(start_hi)), below(x[:, 1], int(num_clips)), (nz * float(noise_scale)).to(torch.float32)

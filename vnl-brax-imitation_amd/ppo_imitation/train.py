@@ -41,6 +41,7 @@ class TrainingState:
     normalizer_params: running_statistics.RunningStatisticsState
     env_steps: int
     policy_counter: Optional[torch.Tensor] = None  # policy_noise="device": the acting policy's step counter, int64 [1]
+    reset_step: Optional[torch.Tensor] = None  # auto_reset="fresh": the step counter of the episode draws, int64 [1]
 
 
 class FlatAdam:
@@ -144,6 +145,7 @@ def train(
     restore_from: Optional[str] = None,
     update_backend: str = "auto",
     policy_noise: str = "generator",
+    auto_reset: str = "first_state",
 ):
     """PPO training (train.py:62-491).
 
@@ -172,6 +174,13 @@ def train(
     `TrainingState.policy_counter` (checkpoint.save_params(policy_counter=...) / `restore_from` carry it).  The PPO update's
     per-minibatch draws stay on the generator.
 
+    `auto_reset`: "first_state" = a finished training env returns to the cached state of its first reset (brax, the
+    reference); "fresh" = it starts a new episode with its own start frame, clip and reset noise, drawn on the device inside
+    the unroll (envs/wrappers.py AutoResetWrapper, vnl_env_reset_done) from streams keyed by (a seed derived from `seed`,
+    step, rank * (num_envs // world) + env index): like the device policy noise, independent of the sharding.  The
+    evaluator's env keeps "first_state" (EvalWrapper scores each env's first episode only).  The counter of the draws is
+    `TrainingState.reset_step` (checkpoint.save_params(reset_step=...) / `restore_from` carry it, like `policy_counter`).
+
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
     ~500 launches of microsecond kernels and purely launch-bound.
@@ -198,7 +207,8 @@ def train(
 
     env = env_wrappers.wrap(environment, episode_length=episode_length, action_repeat=action_repeat,
                             randomization_fn=bind_randomization(randomization_fn, local_envs, seed),
-                            reset_info_on_autoreset=reset_info_on_autoreset)
+                            reset_info_on_autoreset=reset_info_on_autoreset, auto_reset=auto_reset,
+                            auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs)
     env_state = env.reset(g_env)
 
     normalize = (lambda x, y: x)
@@ -227,6 +237,7 @@ def train(
         normalizer_params=running_statistics.init_state(env_state.obs.shape[-1], device=device),
         env_steps=0,
         policy_counter=act_kw.get("counter"),
+        reset_step=env_state.info.get("reset_step"),
     )
 
     if restore_from is not None:
@@ -243,6 +254,8 @@ def train(
         training_state.env_steps = ck.get("env_steps", 0)
         if training_state.policy_counter is not None and "policy_counter" in ck:
             training_state.policy_counter.copy_(ck["policy_counter"])
+        if training_state.reset_step is not None and "reset_step" in ck:  # (the episode draws go on, not from step 0 again)
+            training_state.reset_step.copy_(ck["reset_step"])
 
     from .intention_policy_network import LeafParams
 
@@ -592,7 +605,11 @@ def train(
             training_metrics = training_epoch_with_timing()
             current_step = training_state.env_steps
             if num_resets_per_eval > 0:
+                reset_step = env_state.info.get("reset_step")
                 env_state = env.reset(g_env)
+                if reset_step is not None:  # (auto_reset="fresh": the draws go on where they were, not from step 0 again)
+                    env_state.info["reset_step"].copy_(reset_step)
+                    training_state.reset_step = env_state.info["reset_step"]
         if rank == 0:
             metrics = training_metrics
             if evaluator is not None:
@@ -615,4 +632,5 @@ def train(
     params = inference_params()
     train.last_training_state = training_state  # value net / optimiser for checkpoint-resume (beyond the reference)
     train.last_ppo_network = ppo_network
+    train.last_env_state = env_state  # the training envs as the run leaves them
     return make_policy, params, metrics
