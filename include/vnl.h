@@ -258,7 +258,10 @@ int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* domain, void* s
  * "efc_D", "Jaref", "qfrc_constraint", ...) and its element count; env e is at +e*row_stride.
  * The section "solver_trace" is separate from the image: int32 [num_envs][n_frames][536], the
  * discrete decisions (warm start, iteration counts, line-search bracket decisions, active-row
- * counts) of the solver call of every substep, layout in csrc/vnl_types.h (VNL_TRACE_*). */
+ * counts) of the solver call of every substep, layout in csrc/vnl_types.h (VNL_TRACE_*).
+ * One section is a MODEL table, not per env, and needs no debug mode: "fac_match", the factorisation schedule as the
+ * kernels load it -- uint32 [nv][count] (dev_ptr is that table, to be read as 32-bit words; count = words per ROW), byte
+ * s & 3 of word s >> 2 of row a = the scratch lines row a absorbs in step s, rows padded with zero bytes to whole words. */
 int vnl_env_debug(vnl_env*, int32_t enable, int32_t* row_stride);
 int vnl_env_scratch(const vnl_env*, const char* name, float** dev_ptr, int32_t* count);
 

@@ -22,6 +22,10 @@ OUT = os.path.join(HERE, "libvnl.so")
 #   plain  -DVNL_SOLVER_PLAIN: the solver loop as it was before its per-lane constants were staged -- index tables and friction
 #          read from global memory, a block-descriptor load per product (regression build and bisecting tool for the staged
 #          form, EnvWaveT::with_solve_regs / load_tables: the same values from another place, the same bits on every output)
+#   vmemplain -DVNL_VMEM_PLAIN: the vector-memory accesses of a substep outside the solver loop as they were before they were
+#          taken off the critical path -- factor_aba's schedule byte and 1/D2 store per step, euler()'s element-wise reload of
+#          the second inverse factor, forward()'s copy of the warm start through LO(tmp) (regression build and bisecting tool:
+#          the same values by another route, the same bits on every output; tests/test_gpu_vmem_schedule.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -35,6 +39,7 @@ VARIANTS = {
     "noblk": ("libvnl_noblk.so", ["-DVNL_NO_BLK", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "tail": ("libvnl_tail.so", ["-DVNL_SOLVER_TAIL", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "plain": ("libvnl_plain.so", ["-DVNL_SOLVER_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "vmemplain": ("libvnl_vmemplain.so", ["-DVNL_VMEM_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

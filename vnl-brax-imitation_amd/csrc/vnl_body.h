@@ -243,6 +243,20 @@ VNL_HD S6 mcross_force(S6 v, S6 f) { return S6{cross(v.a, f.a) + cross(v.l, f.l)
 // from the constant block, VnlSpecRodent has them as constants)
 #define MI(f) (SP::fixed ? SP::D.f : m.f)
 #define LO(f) (SP::fixed ? SP::L.f : L.f)
+// A pointer the compiler is TOLD addresses global memory (device code): loads through it are global_load, never flat_load --
+// a flat load counts on the LDS counter too, so every wait for an LDS read behind it also waits for the memory round trip
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VNL_GLOBAL_PTR(T, p) ((const __attribute__((address_space(1))) T*)(p))
+#else
+#define VNL_GLOBAL_PTR(T, p) ((const T*)(p))
+#endif
+// Holds a value just loaded from a table in its register HERE (the empty-asm idiom of with_solve_regs): the loads of a
+// trip named before the first pin are all requested before the one wait, instead of each being sunk to its use
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_VMEM_PLAIN)
+#define VNL_PIN(x) asm volatile("" : "+v"(x))
+#else
+#define VNL_PIN(x) (void)(x)
+#endif
 // Per-lane constants of the solve phase held in REGISTERS (device code; the host simulation reads the tables where they are,
 // and so does the regression build -DVNL_SOLVER_PLAIN, csrc/build.py --plain: today's form of everything the solver loop used
 // to fetch from global memory -- same values, so the same bits on every output)
@@ -359,7 +373,8 @@ struct EnvWaveT {
   VNL_HD vreal* gxquat() const { return st.xquat + (size_t)e * 4 * MI(nbody_out); }
   VNL_HD vreal* gqfrc_act() const { return st.qfrc_actuator + (size_t)e * MI(nv); }
   // library-owned global scratch of this env: the second inverse factor of a substep (invert_aba) and its reciprocal pivots (factor_aba), nM + nv elements
-  VNL_HD vreal* fac2() const { return ev.fac2 + (size_t)e * (MI(nM) + MI(nv)); }
+  // (rows padded to a multiple of four elements: 16-byte aligned in the float build, euler() reloads them four at a time)
+  VNL_HD vreal* fac2() const { return ev.fac2 + (size_t)e * vnl_fac2_stride(MI(nM), MI(nv)); }
   // The model parameters a domain may randomise, every read of them goes through here: the shared DevModel table, or in a
   // randomised instantiation (SP::dom, csrc/vnl_domain.hip) this env's row of the per-env table (global memory, read at the
   // same points).  par: the five tables of vnl_env_set_domain (960 B per env for the rodent); par_row / total_mass_inv
@@ -1093,8 +1108,39 @@ struct EnvWaveT {
     v2r U[NSET][6], diag[NSET];
     vreal S[NSET][6];
     int dep[NSET], ftime[NSET], myline[NSET], adrs[NSET];
+#ifdef VNL_VMEM_PLAIN
     const unsigned char* mt[NSET];
     unsigned nxt[NSET];
+#else
+    // The schedule of a row as 32-bit words, four steps each (the same 8 bits per step), NW of them in registers: the low byte
+    // of the word in use is the step's; every fourth step the next word is picked by its (wave-uniform) index -- a chain of
+    // selects, the held words themselves are never written inside the loop.  A specialised kernel holds the whole row (the
+    // rodent: 9 words), so NO vector-memory instruction lies between the first and the last step; the generic one reloads its
+    // NW words every 4 NW steps -- ONE exposed round trip per 16 steps stays inside its loop.  (NW of a specialisation grows
+    // with the model's fac_steps, a register per four steps and lane set: a much deeper tree wants the window form.)  (One word requested a refill ahead does not help: the compiler copies a loaded word into
+    // its loop-carried register at once, and the wait lands right behind the load.)  1/D2 of the row's own pivot is kept
+    // for ONE store after the loop.
+    constexpr int NW = SP::fixed ? vnl_imax(vnl_fac_stride(SP::D.fac_steps) / 4, 1) : 4;
+    const int nwords = vnl_fac_stride(nsteps) / 4;
+    const auto* mw = VNL_GLOBAL_PTR(unsigned, m.fac_match);
+    unsigned woff[NSET], win[NSET][NW], wcur[NSET];
+    auto pick_word = [&](int q, int i) {
+      unsigned r = win[q][0];
+#pragma unroll
+      for (int k = 1; k < NW; k++) {
+        unsigned w = win[q][k];
+        VNL_PIN(w);  // (a register operand: a chain of selects over array elements is otherwise turned into ONE load at a
+                     // computed index, and the array into scratch memory)
+        r = i == k ? w : r;
+      }
+      return r;
+    };
+    auto load_window = [&](int q, bool ok, int w0) {
+#pragma unroll
+      for (int i = 0; i < NW; i++) win[q][i] = (ok && w0 + i < nwords) ? mw[woff[q] + (unsigned)(w0 + i)] : 0u;
+    };
+    vreal inv2[NSET];
+#endif
 #pragma unroll
     for (int q = 0; q < NSET; q++) {
       const int a = (int)lane + q * VNL_LANES;
@@ -1109,8 +1155,15 @@ struct EnvWaveT {
       adrs[q] = madr(aa), dep[q] = eadr(aa) - adrs[q];
       myline[q] = m.dof_fslot[aa];
       ftime[q] = ok ? m.dof_ftime[aa] : -1;
-      mt[q] = m.fac_match + (size_t)aa * nsteps;
+#ifdef VNL_VMEM_PLAIN
+      mt[q] = m.fac_match + (size_t)aa * vnl_fac_stride(nsteps);
       nxt[q] = (ok && nsteps > 0) ? mt[q][0] : 0u;
+#else
+      woff[q] = (unsigned)(aa * nwords);
+      load_window(q, ok, 0);
+      wcur[q] = win[q][0];
+      inv2[q] = vreal(0.);
+#endif
     }
     VNL_SYNC();  // (crb is read: the image may now grow over it)
     VNL_PROF(7);
@@ -1118,8 +1171,12 @@ struct EnvWaveT {
       unsigned cur[NSET];
 #pragma unroll
       for (int q = 0; q < NSET; q++) {
+#ifdef VNL_VMEM_PLAIN
         cur[q] = nxt[q];
         nxt[q] = (ftime[q] >= 0 && step + 1 < nsteps) ? mt[q][step + 1] : 0u;  // prefetch
+#else
+        cur[q] = wcur[q] & 0xffu, wcur[q] >>= 8;
+#endif
         if (ftime[q] == step) {  // this row is a pivot now: every dof below it has been absorbed
           const int a = (int)lane + q * VNL_LANES;
           v2r D = diag[q];
@@ -1138,7 +1195,11 @@ struct EnvWaveT {
           st4a(vs + 4, v2[0], v2[1], v3_[0], v3_[1]);
           st4a(vs + 8, v4[0], v4[1], v5[0], v5[1]);
           s[LO(dinv) + a] = iv[0];
+#ifdef VNL_VMEM_PLAIN
           g2[MI(nM) + a] = iv[1];
+#else
+          inv2[q] = iv[1];
+#endif
         }
       }
       VNL_WAVE_FENCE();
@@ -1167,7 +1228,22 @@ struct EnvWaveT {
         }
       }
       VNL_WAVE_FENCE();
+#ifndef VNL_VMEM_PLAIN
+      if ((step & 3) == 3) {  // the word is used up: on to the next (the held ones too: the next NW words)
+        const int wi = (step >> 2) + 1;
+#pragma unroll
+        for (int q = 0; q < NSET; q++) {
+          if (!SP::fixed && wi % NW == 0) load_window(q, ftime[q] >= 0, wi);
+          wcur[q] = pick_word(q, wi % NW);
+        }
+      }
+#endif
     }
+#ifndef VNL_VMEM_PLAIN
+#pragma unroll
+    for (int q = 0; q < NSET; q++)  // (a row is a pivot exactly once)
+      if (ftime[q] >= 0) g2[MI(nM) + (int)lane + q * VNL_LANES] = inv2[q];
+#endif
     VNL_SYNC();
     VNL_PROF(8);
     VNL_PROF(9);
@@ -1556,10 +1632,18 @@ struct EnvWaveT {
   // passive + actuation + qfrc_smooth + qacc_smooth
   VNL_HD void smooth_forces() const {
     VNL_FOR(j, MI(njnt)) {
+#ifdef VNL_VMEM_PLAIN
       if (m.jnt_type[j] == VNL_JNT_HINGE) {
         vreal k = m.jnt_stiffness[j];
         if (k != vreal(0.)) s[LO(smooth) + m.jnt_dofadr[j]] -= k * (s[LO(qpos) + m.jnt_qposadr[j]] - m.jnt_springref[j]);
       }
+#else
+      // (the five table reads of a joint in ONE round trip, not one behind the other under the two conditions)
+      int type = m.jnt_type[j], da = m.jnt_dofadr[j], qa = m.jnt_qposadr[j];
+      vreal k = m.jnt_stiffness[j], ref = m.jnt_springref[j];
+      VNL_PIN(type); VNL_PIN(da); VNL_PIN(qa); VNL_PIN(k); VNL_PIN(ref);
+      if (type == VNL_JNT_HINGE && k != vreal(0.)) s[LO(smooth) + da] -= k * (s[LO(qpos) + qa] - ref);
+#endif
     }
     // Actuator forces in parallel (the model tables are L2 reads: the former one-lane loop paid 30 latencies in a
     // row).  Several actuators may drive one dof, so each dof's lane then walks the actuator list in order and
@@ -2256,12 +2340,22 @@ struct EnvWaveT {
     }
   }
 
-  // forward.forward.  `warm` = qacc_warmstart (HBM on the first substep, LDS qacc afterwards).
-  VNL_HD void forward(const vreal* warm) const {
+  // forward.forward.  `gwarm` = qacc_warmstart in global memory (the first substep of a step), or null: LO(qacc) holds it
+  // already (the substeps after it: euler() left it there; a reset: zero).
+  VNL_HD void forward(const vreal* gwarm) const {
+#ifdef VNL_VMEM_PLAIN
+    const vreal* warm = gwarm ? gwarm : s + LO(qacc);
     VNL_FOR(d, MI(nv)) s[LO(tmp) + d] = warm[d];
     VNL_SYNC();
     VNL_FOR(d, MI(nv)) s[LO(qacc) + d] = s[LO(tmp) + d];
     VNL_SYNC();
+#else
+    if (gwarm) {
+      const auto* gw = VNL_GLOBAL_PTR(vreal, gwarm);
+      VNL_FOR(d, MI(nv)) s[LO(qacc) + d] = gw[d];
+      VNL_SYNC();
+    }
+#endif
     // Timing knob (VNL_DBG_REPEAT=stage:count at env creation; 0 in normal use): run one stage
     // `count` extra times on data that is recomputed afterwards, so results are unchanged and the
     // wall-time difference prices that stage in the real (uninstrumented) build.
@@ -2388,6 +2482,48 @@ struct EnvWaveT {
   VNL_HD void euler() const {
     const int nv = MI(nv);
     VNL_PROF(26);  // the tail of solve()
+#ifndef VNL_VMEM_PLAIN
+    if (MI(eulerdamp) && factor_pair_ok()) {
+      // the INVERTED factor of M + h diag(damping) was made beside M's by forward() (factor_aba + invert_aba): bring it
+      // into the pool (the constraint rows are dead now) and apply it.  All of a lane's loads are requested before the first
+      // LDS write -- four elements each, the whole row in ONE round trip for the rodent (five per lane) -- and before the
+      // right-hand side is formed, which runs under their latency.
+      constexpr int NB = SP::fixed ? (vnl_fac2_stride(SP::D.nM, SP::D.nv) / 4 + VNL_LANES - 1) / VNL_LANES : 4;
+      const auto* g2 = VNL_GLOBAL_PTR(vreal, fac2());
+      const int n2 = MI(nM) + MI(nv), n2p = vnl_fac2_stride(MI(nM), MI(nv));
+      VNL_SYNC_GLOBAL();  // (written by factor_aba / invert_aba, one row per lane; read here across lanes)
+      bool rhs = false;
+      for (int k0 = 4 * (int)lane; !rhs || k0 < n2p; k0 += 4 * VNL_LANES * NB) {
+        R4 x[NB];
+#pragma unroll
+        for (int t = 0; t < NB; t++) {
+          const int k = k0 + 4 * VNL_LANES * t;
+          if (k < n2p) x[t] = ld4a(g2 + k);
+        }
+        if (!rhs) {
+          // (no join between this and the writes to LO(P) below: the pool does not overlap smooth / qfrc_c / tmp, and one
+          // wave's LDS operations execute in issue order; the join before solve_inplace orders both against its reads)
+          VNL_FOR(d, nv) s[LO(tmp) + d] = s[LO(smooth) + d] + s[LO(qfrc_c) + d];
+          rhs = true;
+        }
+#pragma unroll
+        for (int t = 0; t < NB; t++) {
+          const int k = k0 + 4 * VNL_LANES * t;
+          if (k + 3 < n2) {
+            s[LO(P) + k] = x[t].x, s[LO(P) + k + 1] = x[t].y, s[LO(P) + k + 2] = x[t].z, s[LO(P) + k + 3] = x[t].w;
+          } else if (k < n2) {  // (the row's last elements; the padding behind them is never written)
+            s[LO(P) + k] = x[t].x;
+            if (k + 1 < n2) s[LO(P) + k + 1] = x[t].y;
+            if (k + 2 < n2) s[LO(P) + k + 2] = x[t].z;
+          }
+        }
+      }
+      VNL_SYNC();
+      fresh().with_solve_regs(false).solve_inplace(LO(tmp), LO(P), LO(P) + MI(nM));
+      VNL_PROF(27);
+    } else
+#endif
+    {
     VNL_FOR(d, nv) s[LO(tmp) + d] = MI(eulerdamp) ? s[LO(smooth) + d] + s[LO(qfrc_c) + d] : s[LO(qacc) + d];
     VNL_SYNC();
     if (MI(eulerdamp) && factor_pair_ok()) {
@@ -2408,6 +2544,7 @@ struct EnvWaveT {
       fresh().invert_factor();
       fresh().with_solve_regs(false).solve_inplace(LO(tmp));
       VNL_PROF(27);
+    }
     }
     VNL_FOR(i, MI(nu)) {
       if (m.act_tau[i] >= vreal(0.)) s[LO(act) + i] += s[LO(actdot) + i] * m.dt;
@@ -2599,7 +2736,7 @@ struct EnvWaveT {
     VNL_FOR(i, MI(nu)) s[LO(act) + i] = vreal(0.), s[LO(ctrl) + i] = vreal(0.);
     VNL_FOR(d, MI(nv)) s[LO(qacc) + d] = vreal(0.);
     VNL_SYNC();
-    with_trace(trace_of(trace_base, 0)).forward(s + LO(qacc));  // qacc_warmstart = 0 (mjx.make_data)
+    with_trace(trace_of(trace_base, 0)).forward(nullptr);  // qacc_warmstart = 0 (mjx.make_data), in LO(qacc)
     VNL_SYNC_GLOBAL();
     store_state();
     write_traj(clip, sf);
@@ -2734,7 +2871,7 @@ struct EnvWaveT {
     }
     VNL_PROF(29);  // tables, state load, rtrunk
     for (int f = 0; f < ev.n_frames; f++) {
-      fresh().with_trace(trace_of(trace_base, f)).forward(f == 0 ? gw : s + LO(qacc));
+      fresh().with_trace(trace_of(trace_base, f)).forward(f == 0 ? gw : nullptr);
       if (dump_mid && f == ev.n_frames - 1) dump(dump_mid);  // the LDS image as the last forward pass leaves it
       fresh().euler();
     }

@@ -667,8 +667,9 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
       }
     }
     {  // fac_match[a][t]: the scratch lines whose pivot of step t lies strictly below row a (factor_aba absorbs them)
-      const int nst = d.fac_steps;
-      std::vector<unsigned char> match((size_t)nv * (nst > 0 ? nst : 1), 0);
+      // (rows padded to whole 32-bit words, four steps each: the kernel loads a row's schedule by the word)
+      const int nst = vnl_fac_stride(d.fac_steps);
+      std::vector<unsigned char> match((size_t)nv * (nst > 0 ? nst : 4), 0);
       for (int j = 0; j < nv; j++)
         for (int a = par[j]; a >= 0; a = par[a]) match[(size_t)a * nst + ftime[j]] |= (unsigned char)(1u << fslot[j]);
       const unsigned char* dp = nullptr;
@@ -932,8 +933,10 @@ extern "C" int vnl_env_create(const vnl_model* hm, const vnl_envspec* es, int32_
 #undef UP
   {
     void* p = nullptr;
-    HIPCHK(hipMalloc(&p, (size_t)num_envs * (d.nM + d.nv) * sizeof(vreal)));
+    const size_t n2 = (size_t)num_envs * vnl_fac2_stride(d.nM, d.nv) * sizeof(vreal);
+    HIPCHK(hipMalloc(&p, n2));
     env->allocs.push_back(p);
+    HIPCHK(hipMemset(p, 0, n2));  // (the padding of a row is read with it, never used)
     e.fac2 = (vreal*)p;
   }
   {
@@ -1021,6 +1024,11 @@ extern "C" int vnl_env_scratch(const vnl_env* env, const char* name, float** dev
         return VNL_OK;
       }
     return fail(VNL_ERR_ARG, "unknown scratch section %s", name);
+  }
+  if (strcmp(name, "fac_match") == 0) {  // the factorisation schedule as the kernels load it: [nv][count] 32-bit words (no debug needed)
+    *dev_ptr = (float*)env->dm.fac_match;
+    *count = vnl_fac_stride(env->dm.fac_steps) / 4;
+    return VNL_OK;
   }
   if (!env->dump) return fail(VNL_ERR_ARG, "scratch dump is off: call vnl_env_debug(env, 1) before reset/step");
   if (strcmp(name, "solver_trace") == 0) {  // int32 [num_envs][n_frames][VNL_TRACE_INTS], contiguous (not inside the image)

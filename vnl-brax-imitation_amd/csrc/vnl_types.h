@@ -86,7 +86,7 @@ struct DevModel {
   const int* fac_guest;              /* [64] row 64.. that lane l inverts after its own row (EnvWave::invert_aba; -1: none); null if
                                         the model has no such rows or they cannot be placed (host depth <= 12, guest depth <= 24) */
   const unsigned* blk_tab;           /* [trips_row x 64 | trips_col x 64] block descriptors of blk_apply (vnl_lib.hip builds them); null if blk_cfg == 0 */
-  const unsigned char* fac_match;    /* [nv][fac_steps]: bit k set = row a absorbs the pivot published in scratch line k in that step */
+  const unsigned char* fac_match;    /* [nv][vnl_fac_stride(fac_steps)], 4-byte aligned: bit k set = row a absorbs the pivot published in scratch line k in that step */
   const int *dof_ndesc;              /* descendants of dof a are dofs a+1 .. a+ndesc[a] (DFS numbering) */
   const unsigned char* lvl_tab;      /* [nv] dofs sorted by depth, then [max_depth+2] level starts */
   const vreal *dof_armature, *dof_damping;
@@ -108,7 +108,7 @@ struct DevEnv {
   const int *body_idxs, *end_eff_idx, *app_body, *app_ref_col, *joint_cols;
   const float *position, *quaternion, *joints, *body_positions, *velocity, *angular_velocity, *joints_velocity;
   const float* center_of_mass; /* (C,T,3) or null: reference for rcom (else body_positions[com_ref_col]) */
-  vreal* fac2; /* library-owned scratch [num_envs][nM + nv]: the second inverse factor of a substep (EnvWave::invert_aba) */
+  vreal* fac2; /* library-owned scratch [num_envs][vnl_fac2_stride(nM, nv)]: the second inverse factor of a substep (EnvWave::invert_aba) */
 };
 
 // caller-owned buffers, row-major [env][feature] (see include/vnl.h vnl_state)
@@ -229,6 +229,12 @@ constexpr int vnl_cvel_at(int P, int smooth, int nbody, int nv) {
   const int a = P + 16 * nbody, b = vnl_vstore(P) + 12 * nv;
   return (b > a && b + 6 * nbody <= smooth) ? b : a;
 }
+
+/* Row strides of two tables the host and the kernels must agree on: a row of DevModel::fac_match in bytes (whole 32-bit words,
+ * four steps each: EnvWaveT::factor_aba loads its schedule by the word) and a row of DevEnv::fac2 in elements (a multiple of
+ * four: EnvWaveT::euler reloads it four elements at a time, 16-byte aligned in the float build) */
+constexpr int vnl_fac_stride(int fac_steps) { return (fac_steps + 3) & ~3; }
+constexpr int vnl_fac2_stride(int nM, int nv) { return (nM + nv + 3) & ~3; }
 
 /* Compile-time model of a kernel specialisation.  `fixed == false`: every dimension and LDS offset is read from the constant
  * block at run time (any model the library accepts).  `fixed == true`: they are the constants below -- loop bounds fold,
