@@ -26,6 +26,11 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          taken off the critical path -- factor_aba's schedule byte and 1/D2 store per step, euler()'s element-wise reload of
 #          the second inverse factor, forward()'s copy of the warm start through LO(tmp) (regression build and bisecting tool:
 #          the same values by another route, the same bits on every output; tests/test_gpu_vmem_schedule.py)
+#   ldsplain -DVNL_LDS_PLAIN: the serial LDS round trips of a substep as they were before they were taken out -- blk_apply one
+#          trip after the other (indices, gathers, the writer's operands: three dependent round trips each), factor_aba's
+#          pivot block writing V = U / D and 1/D1 inside the step chain and its lane sets reading their lines one after the
+#          other, the solver's qg1 / qg2 / Gauss scalars in per-dof passes of their own (regression build and bisecting tool:
+#          the same operations in another order of issue, the same bits on every output; tests/test_gpu_lds_chain.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -40,6 +45,7 @@ VARIANTS = {
     "tail": ("libvnl_tail.so", ["-DVNL_SOLVER_TAIL", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "plain": ("libvnl_plain.so", ["-DVNL_SOLVER_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "vmemplain": ("libvnl_vmemplain.so", ["-DVNL_VMEM_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "ldsplain": ("libvnl_ldsplain.so", ["-DVNL_LDS_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

@@ -30,6 +30,9 @@
 //     the factor (L' D L).
 #pragma once
 #include <math.h>
+#ifdef VNL_FORKJOIN_DEFINED /* the host simulation: blk_apply asserts what its phase form relies on */
+#include <assert.h>
+#endif
 
 #include "vnl_types.h"
 
@@ -256,6 +259,14 @@ VNL_HD S6 mcross_force(S6 v, S6 f) { return S6{cross(v.a, f.a) + cross(v.l, f.l)
 #define VNL_PIN(x) asm volatile("" : "+v"(x))
 #else
 #define VNL_PIN(x) (void)(x)
+#endif
+// VNL_PIN in EVERY device build (VNL_PIN itself is a scheduling aid and is off under -DVNL_VMEM_PLAIN): the operands of an
+// expression, or one of its products, held in a register as a read-back from LDS would leave them, so that the compiler
+// neither folds a negation into the products nor chooses another product to round first (solve()'s carried scalars).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VNL_OPAQUE(x) asm volatile("" : "+v"(x))
+#else
+#define VNL_OPAQUE(x) (void)(x)
 #endif
 // Per-lane constants of the solve phase held in REGISTERS (device code; the host simulation reads the tables where they are,
 // and so does the regression build -DVNL_SOLVER_PLAIN, csrc/build.py --plain: today's form of everything the solver loop used
@@ -1139,7 +1150,14 @@ struct EnvWaveT {
 #pragma unroll
       for (int i = 0; i < NW; i++) win[q][i] = (ok && w0 + i < nwords) ? mw[woff[q] + (unsigned)(w0 + i)] : 0u;
     };
+#ifdef VNL_LDS_PLAIN
     vreal inv2[NSET];
+#endif
+#endif
+#ifndef VNL_LDS_PLAIN
+    v2r ivp[NSET];  // (1/D1, 1/D2) of the row's own pivot, kept for the pass after the loop
+#pragma unroll
+    for (int q = 0; q < NSET; q++) ivp[q] = v2r{vreal(0.), vreal(0.)};
 #endif
 #pragma unroll
     for (int q = 0; q < NSET; q++) {
@@ -1162,7 +1180,9 @@ struct EnvWaveT {
       woff[q] = (unsigned)(aa * nwords);
       load_window(q, ok, 0);
       wcur[q] = win[q][0];
+#ifdef VNL_LDS_PLAIN
       inv2[q] = vreal(0.);
+#endif
 #endif
     }
     VNL_SYNC();  // (crb is read: the image may now grow over it)
@@ -1178,7 +1198,6 @@ struct EnvWaveT {
         cur[q] = wcur[q] & 0xffu, wcur[q] >>= 8;
 #endif
         if (ftime[q] == step) {  // this row is a pivot now: every dof below it has been absorbed
-          const int a = (int)lane + q * VNL_LANES;
           v2r D = diag[q];
 #pragma unroll
           for (int i = 0; i < 6; i++) D += v2r{S[q][i], S[q][i]} * U[q][i];
@@ -1188,17 +1207,26 @@ struct EnvWaveT {
           st4a(ln + 4, U[q][2][0], U[q][2][1], U[q][3][0], U[q][3][1]);
           st4a(ln + 8, U[q][4][0], U[q][4][1], U[q][5][0], U[q][5][1]);
           st4a(ln + 12, iv[0], iv[1], (vreal)(adrs[q] + dep[q]), vreal(0.));
+#ifndef VNL_LDS_PLAIN
+          // (the line is all the ancestors wait for.  What stays -- V = U / D, 1/D1 -- is read by invert_aba and the products
+          // only: U and 1/D of a row are final once it has been a pivot, every dof below it is absorbed, so they are written
+          // by all lanes at once after the loop, like 1/D2, and the absorbers' line reads do not queue behind those writes)
+          ivp[q] = iv;
+#else
           // what stays: V = U / D of both systems (invert_aba), 1/D1 where every M^-1 product expects it, 1/D2 beside N2
+          const int a = (int)lane + q * VNL_LANES;
           vreal* vs = s + VS + 12 * a;
           const v2r v0 = U[q][0] * iv, v1 = U[q][1] * iv, v2 = U[q][2] * iv, v3_ = U[q][3] * iv, v4 = U[q][4] * iv, v5 = U[q][5] * iv;
           st4a(vs, v0[0], v0[1], v1[0], v1[1]);
           st4a(vs + 4, v2[0], v2[1], v3_[0], v3_[1]);
           st4a(vs + 8, v4[0], v4[1], v5[0], v5[1]);
           s[LO(dinv) + a] = iv[0];
-#ifdef VNL_VMEM_PLAIN
-          g2[MI(nM) + a] = iv[1];
-#else
+#ifndef VNL_VMEM_PLAIN
           inv2[q] = iv[1];
+#endif
+#endif
+#ifdef VNL_VMEM_PLAIN  // (the former per-step store of 1/D2, in either form of the block)
+          g2[MI(nM) + (int)lane + q * VNL_LANES] = iv[1];
 #endif
         }
       }
@@ -1208,13 +1236,31 @@ struct EnvWaveT {
 #pragma unroll
         for (int q = 0; q < NSET; q++) more = more || cur[q] != 0u;
         if (!vnl_wave_any(more)) break;
+#ifndef VNL_LDS_PLAIN
+        // the lines of ALL lane sets are requested before any set absorbs (the sets' registers are disjoint): one LDS round
+        // trip per pass where a set after the other pays one each.  (A set without work in this pass requests nothing; a
+        // lane without work in a set that has some reads line 0.)
+        R4 lu0[NSET], lu1[NSET], lu2[NSET], lhd[NSET];
+#pragma unroll
+        for (int q = 0; q < NSET; q++) {
+          if (vnl_wave_any(cur[q] != 0u)) {
+            const vreal* ln = s + sc + (cur[q] != 0u ? __builtin_ctz(cur[q]) : 0) * LW;
+            lu0[q] = ld4a(ln), lu1[q] = ld4a(ln + 4), lu2[q] = ld4a(ln + 8), lhd[q] = ld4a(ln + 12);
+          }
+        }
+#endif
 #pragma unroll
         for (int q = 0; q < NSET; q++) {
           if (cur[q] != 0u) {
+#ifndef VNL_LDS_PLAIN
+            cur[q] &= cur[q] - 1u;
+            const R4 u0 = lu0[q], u1 = lu1[q], u2 = lu2[q], hd = lhd[q];
+#else
             const int k = __builtin_ctz(cur[q]);
             cur[q] &= cur[q] - 1u;
             const vreal* ln = s + sc + k * LW;
             const R4 u0 = ld4a(ln), u1 = ld4a(ln + 4), u2 = ld4a(ln + 8), hd = ld4a(ln + 12);
+#endif
             const v2r Uk[6] = {v2r{u0.x, u0.y}, v2r{u0.z, u0.w}, v2r{u1.x, u1.y}, v2r{u1.z, u1.w}, v2r{u2.x, u2.y}, v2r{u2.z, u2.w}};
             v2r pa = v2r{S[q][0], S[q][0]} * Uk[0], pb = v2r{S[q][1], S[q][1]} * Uk[1];
             pa += v2r{S[q][2], S[q][2]} * Uk[2], pb += v2r{S[q][3], S[q][3]} * Uk[3];
@@ -1239,7 +1285,25 @@ struct EnvWaveT {
       }
 #endif
     }
+#ifndef VNL_LDS_PLAIN
+#pragma unroll
+    for (int q = 0; q < NSET; q++) {  // what stays, all rows at once (a row is a pivot exactly once: U[q] and ivp[q] are its final ones)
+      if (ftime[q] >= 0) {
+        const int a = (int)lane + q * VNL_LANES;
+        const v2r iv = ivp[q];
+        // V = U / D of both systems (invert_aba), 1/D1 where every M^-1 product expects it, 1/D2 beside N2
+        vreal* vs = s + VS + 12 * a;
+        const v2r v0 = U[q][0] * iv, v1 = U[q][1] * iv, v2 = U[q][2] * iv, v3_ = U[q][3] * iv, v4 = U[q][4] * iv, v5 = U[q][5] * iv;
+        st4a(vs, v0[0], v0[1], v1[0], v1[1]);
+        st4a(vs + 4, v2[0], v2[1], v3_[0], v3_[1]);
+        st4a(vs + 8, v4[0], v4[1], v5[0], v5[1]);
+        s[LO(dinv) + a] = iv[0];
 #ifndef VNL_VMEM_PLAIN
+        g2[MI(nM) + a] = iv[1];
+#endif
+      }
+    }
+#elif !defined(VNL_VMEM_PLAIN)
 #pragma unroll
     for (int q = 0; q < NSET; q++)  // (a row is a pivot exactly once)
       if (ftime[q] >= 0) g2[MI(nM) + (int)lane + q * VNL_LANES] = inv2[q];
@@ -1457,6 +1521,7 @@ struct EnvWaveT {
 #pragma unroll
     for (int t = 0; t < MAXT; t++) pre[t] = t < trips ? tab[t * 64 + (int)lane] : 0u;
 #endif
+#ifdef VNL_LDS_PLAIN  // the former form: a trip after the other, three dependent LDS round trips each
 #pragma unroll
     for (int trip = 0; trip < MAXT; trip++) {
       if (trip >= trips) break;
@@ -1511,6 +1576,129 @@ struct EnvWaveT {
         }
       }
     }
+#else
+    // The trips of a product IN PHASES, a window of PH trips at a time: (1) every trip's index reads, and in the same burst
+    // what does not depend on them -- the row form's factor entries, the column form's in[] run, the writer's in[r] and
+    // dinv[r] (the descriptor names r; a lane that writes nothing reads element r = its descriptor's row all the same, which
+    // is inside the vectors) --, (2) every trip's gathers, (3) the products and segment sums, (4) the writes.  ONE chain of
+    // two dependent round trips per window where a trip after the other pays three each: the compiler cannot move a trip's
+    // reads above the trip before's write itself, a gathered address may be the element just written for all it knows.
+    // It is not: the phase form RELIES on in != out and on out[] overlapping neither the factor image nor dinv[]
+    // (solve_inplace, mass_mul_factor: the callers say why that holds; asserted in the host build), so no trip reads
+    // what another trip of the same product wrote.  Sums, selects and the acc expression are those of the former form.
+    // (PH = 2: the rodent's tables have two trips per form.  A table with more trips goes window after window, which holds
+    // the registers of a phase down to 2 x (13 + 13 + 13).)
+    constexpr int PH = 2;
+#ifdef VNL_FORKJOIN_DEFINED
+    assert(in != out && (in + MI(nv) <= out || out + MI(nv) <= in));
+    assert(out + MI(nv) <= LDb || LDb + ST * MI(nM) <= out);
+    assert(out + MI(nv) <= dinvb || dinvb + ST * MI(nv) <= out);
+#endif
+#pragma unroll
+    for (int t0 = 0; t0 < MAXT; t0 += PH) {
+      if (t0 >= trips) break;
+      VNL_PERLANE(vreal, part[PH]);
+      VNL_PERLANE(unsigned, dsc[PH]);
+      VNL_PERLANE(vreal, xin[PH]);  // in[r], dinv[r] of the element this lane writes
+      VNL_PERLANE(vreal, dv[PH]);
+      VNL_FOR(l, VNL_WAVE_ITEMS(64)) {
+        unsigned d[PH];
+        int idx[PH][W];
+        vreal l_[PH][W], x[PH][W];
+#pragma unroll
+        for (int k = 0; k < PH; k++) {  // (1)
+          const int trip = t0 + k;
+          if (trip >= trips) break;
+#ifdef __HIP_DEVICE_COMPILE__
+          d[k] = (VNL_SOLVE_REGS && (sr.on & VNL_SR_BLK) && trip < VNL_BLK_REGS) ? sr.blk[COL ? 1 : 0][trip] : pre[trip];
+#else
+          d[k] = tab[trip * 64 + l];
+#endif
+          // (entries past the block's own n are read -- they are inside the LDS image: the next row's entries, the next
+          // table -- and dropped by the selects below, which costs less than clamping every index)
+          if constexpr (!COL) {
+            const int e0 = (int)(d[k] & 0xffffu);
+            const unsigned char* an = (const unsigned char*)(s + LO(tab_anc)) + e0;
+            const vreal* row = s + LDb + ST * e0;
+#pragma unroll
+            for (int u = 0; u < W; u++) idx[k][u] = an[u], l_[k][u] = row[ST * u];
+          } else {
+            const int i0 = (int)(d[k] & 0x7fu);
+            const unsigned short* ea = (const unsigned short*)(s + LO(tab_madr)) + MI(nv) + i0;
+#pragma unroll
+            for (int u = 0; u < W; u++) idx[k][u] = ea[u], x[k][u] = s[in + i0 + u];
+          }
+          const int r = (int)(d[k] >> 20) & 0x7f;
+#ifdef VNL_FORKJOIN_DEFINED
+          assert(r < MI(nv));  // (every lane reads in[r] / dinv[r], writer or not: an empty descriptor names row 0)
+#endif
+          VNL_AT(xin[k], l) = s[in + r];
+          VNL_AT(dv[k], l) = dmode != 0 ? s[dinvb + ST * r] : vreal(0.);
+        }
+        // (the pins: every index of the window is in its register here and every gathered value below, all requested
+        // before the one wait -- the compiler otherwise moves the reads of a block's last entry, index and gather, into a
+        // branch on n of their own: two more dependent round trips)
+#pragma unroll
+        for (int k = 0; k < PH; k++) {
+          if (t0 + k >= trips) break;
+#pragma unroll
+          for (int u = 0; u < W; u++) VNL_PIN(idx[k][u]);
+        }
+#pragma unroll
+        for (int k = 0; k < PH; k++) {  // (2)
+          if (t0 + k >= trips) break;
+          if constexpr (!COL) {
+#pragma unroll
+            for (int u = 0; u < W; u++) x[k][u] = s[in + idx[k][u]];
+          } else {
+            const vreal* ld = s + LDb - ST * ((int)(d[k] >> 7) & 0x3f);
+#pragma unroll
+            for (int u = 0; u < W; u++) l_[k][u] = ld[ST * idx[k][u]];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < PH; k++) {
+          if (t0 + k >= trips) break;
+#pragma unroll
+          for (int u = 0; u < W; u++) {
+            if constexpr (!COL) VNL_PIN(x[k][u]);
+            else VNL_PIN(l_[k][u]);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < PH; k++) {  // (3)
+          if (t0 + k >= trips) break;
+          const int n = (int)(d[k] >> 16) & 15;
+          vreal p0 = vreal(0.), p1 = vreal(0.);
+#pragma unroll
+          for (int u = 0; u < W; u++) {
+            const vreal pr = u < n ? l_[k][u] * x[k][u] : vreal(0.);
+            if (u & 1) p1 += pr;
+            else p0 += pr;
+          }
+          VNL_AT(part[k], l) = p0 + p1;
+          VNL_AT(dsc[k], l) = d[k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < PH; k++) {
+        if (t0 + k >= trips) break;
+        VNL_SEG_SUM(part[k], dsc[k], steps);
+      }
+      VNL_FOR(l, VNL_WAVE_ITEMS(64)) {  // (4)
+#pragma unroll
+        for (int k = 0; k < PH; k++) {
+          if (t0 + k >= trips) break;
+          const unsigned d = VNL_AT(dsc[k], l);
+          if (d & (1u << 27)) {
+            const int r = (int)(d >> 20) & 0x7f;
+            const vreal acc = VNL_AT(xin[k], l) + VNL_AT(part[k], l);
+            s[out + r] = dmode == 1 ? acc * VNL_AT(dv[k], l) : (dmode == 2 ? acc / VNL_AT(dv[k], l) : acc);
+          }
+        }
+      }
+    }
+#endif
     VNL_SYNC();
   }
 
@@ -1522,6 +1710,8 @@ struct EnvWaveT {
 #endif
   }
   // x <- M^-1 x = L^-1 D^-1 L^-T x with the inverted factor: two dependency-free sparse products
+  // (blk_apply's phase form wants in != out and out[] clear of the factor image and dinv[]: x -> LO(tmp2) -> x, and neither
+  // x -- a CG vector, euler()'s LO(tmp) -- nor LO(tmp2) lies in LO(LD) / LO(dinv), euler()'s copy in LO(P) or the Hessian image)
   VNL_HD void solve_inplace(int x, int LDb, int dinvb) const {
     if (blk_on()) {
       blk_apply<1, true>(x, LO(tmp2), 1, LDb, dinvb);
@@ -1534,6 +1724,7 @@ struct EnvWaveT {
   VNL_HD void solve_inplace(int x) const { solve_inplace(x, LO(LD), LO(dinv)); }
 
   // out = M v = L' D L v with the (not yet inverted) factor
+  // (blk_apply's phase form: vec -> LO(tmp2) -> out with vec = LO(qacc), out = LO(mv), all three apart and outside LO(LD) / LO(dinv))
   VNL_HD void mass_mul_factor(int vec, int out) const {
     if (blk_on()) {
       blk_apply<1, false>(vec, LO(tmp2), 2, LO(LD), LO(dinv));
@@ -2234,13 +2425,33 @@ struct EnvWaveT {
     const bool newton = MI(solver_newton) != 0;
     if (newton) fresh().newton_solve(LO(Mgrad));
     else fresh().solve_inplace(LO(Mgrad));
+    // .. and so are the two scalars of the line search's Gauss polynomial, qg1 = search . (Ma - smooth) and qg2 = search . mv / 2:
+    // Ma and smooth do not change between the loop that writes search / mv and the line search (CG route; on the Newton route
+    // mv is made by newton_mass_mul afterwards, and the pass of their own stays), and the Gauss term g of the new point is
+    // accumulated where qacc / Ma are updated.  -DVNL_LDS_PLAIN (csrc/build.py --ldsplain) keeps the three passes.
+#ifdef VNL_LDS_PLAIN
+    const bool qg_carried = false;
+#else
+    const bool qg_carried = !newton;
+#endif
+    vreal qg1c = vreal(0.), qg2c = vreal(0.);
     VNL_FOR(d, nv) {
       const vreal mg = s[LO(Mgrad) + d], gr = s[LO(grad) + d];
       s[LO(search) + d] = -mg;
       s[LO(mv) + d] = -gr;  // M search (CG: search = -M^-1 grad)
       ss += mg * mg, gp += gr * mg;
+      if (qg_carried) {
+        // (pinned: the values as the pass of their own read them back, opaque to the optimiser -- it otherwise folds the
+        // negations into the products and rounds the other product of qg1's difference first)
+        vreal sd = -mg, md = -gr;
+        VNL_OPAQUE(sd);
+        VNL_OPAQUE(md);
+        qg1c += sd * s[LO(Ma) + d] - sd * s[LO(smooth) + d];
+        qg2c += sd * md;
+      }
     }
     ss = vnl_wave_sum(ss), gp = vnl_wave_sum(gp);
+    if (qg_carried) qg1c = vnl_wave_sum(qg1c), qg2c = vreal(0.5) * vnl_wave_sum(qg2c);
     VNL_SYNC();
     if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
     VNL_PROF(15);
@@ -2255,13 +2466,16 @@ struct EnvWaveT {
       VNL_PROF(16);
       fresh().jac_mul(LO(search), LO(jv), false);
       VNL_PROF(17);
-      vreal qg1 = vreal(0.), qg2 = vreal(0.);
-      VNL_FOR(d, nv) {
-        vreal sd = s[LO(search) + d];
-        qg1 += sd * s[LO(Ma) + d] - sd * s[LO(smooth) + d];
-        qg2 += sd * s[LO(mv) + d];
+      vreal qg1 = qg1c, qg2 = qg2c;
+      if (!qg_carried) {
+        qg1 = vreal(0.), qg2 = vreal(0.);
+        VNL_FOR(d, nv) {
+          vreal sd = s[LO(search) + d];
+          qg1 += sd * s[LO(Ma) + d] - sd * s[LO(smooth) + d];
+          qg2 += sd * s[LO(mv) + d];
+        }
+        qg1 = vnl_wave_sum(qg1), qg2 = vreal(0.5) * vnl_wave_sum(qg2);
       }
-      qg1 = vnl_wave_sum(qg1), qg2 = vreal(0.5) * vnl_wave_sum(qg2);
       VNL_PROF(18);
       int* tr = (trace && it < VNL_TRACE_ITERS) ? trace + 8 + VNL_TRACE_REC * it : nullptr;
       if (trace) {
@@ -2277,10 +2491,23 @@ struct EnvWaveT {
                         ? fresh().template line_search<2, true>(gauss, qg1, qg2, gtol, tr)
                         : ((MI(nefc) <= 5 * VNL_LANES) ? fresh().template line_search<VNL_ROWS_SMALL>(gauss, qg1, qg2, gtol, tr)
                                                      : fresh().template line_search<VNL_ROWS_PER_LANE>(gauss, qg1, qg2, gtol, tr));
+#ifdef VNL_LDS_PLAIN
       VNL_FOR(d, nv) {
         s[LO(qacc) + d] += alpha * s[LO(search) + d];
         s[LO(Ma) + d] += alpha * s[LO(mv) + d];
       }
+#else
+      vreal g = vreal(0.);  // the Gauss term at the new point, from the values as they are stored (used below unless the pass is the last)
+      VNL_FOR(d, nv) {
+        vreal qa = s[LO(qacc) + d], ma = s[LO(Ma) + d];
+        qa += alpha * s[LO(search) + d];
+        ma += alpha * s[LO(mv) + d];
+        VNL_OPAQUE(qa);
+        VNL_OPAQUE(ma);  // (the stored values, as the pass of its own read them back)
+        s[LO(qacc) + d] = qa, s[LO(Ma) + d] = ma;
+        g += (ma - s[LO(smooth) + d]) * (qa - s[LO(qacc_smooth) + d]);
+      }
+#endif
       VNL_PROF(19);
       for_live_rows([&](int r) { s[LO(Jaref) + r] += alpha * s[LO(jv) + r]; });
       VNL_SYNC();
@@ -2299,8 +2526,10 @@ struct EnvWaveT {
       }
 #endif
       // ---- constraint + gradient update   (gp = grad . Mgrad of the vectors as they stand: carried, see above)
+#ifdef VNL_LDS_PLAIN
       vreal g = vreal(0.);
       VNL_FOR(d, nv) g += (s[LO(Ma) + d] - s[LO(smooth) + d]) * (s[LO(qacc) + d] - s[LO(qacc_smooth) + d]);
+#endif
       g = vnl_wave_sum(g);
       VNL_PROF(21);
       vreal ncost = fresh().constraint_force() + vreal(0.5) * g;
@@ -2325,6 +2554,7 @@ struct EnvWaveT {
       if (newton) beta = vreal(0.);  // solver.solve: search = -Mgrad
       gp = d2;  // grad . Mgrad with Mgrad := tmp below
       ss = vreal(0.);
+#ifdef VNL_LDS_PLAIN
       VNL_FOR(d, nv) {
         vreal mg = s[LO(tmp) + d];
         s[LO(Mgrad) + d] = mg;
@@ -2333,7 +2563,26 @@ struct EnvWaveT {
         s[LO(mv) + d] = -s[LO(grad) + d] + beta * s[LO(mv) + d];
         ss += sn * sn;
       }
+#else
+      qg1c = vreal(0.), qg2c = vreal(0.);
+      VNL_FOR(d, nv) {
+        vreal mg = s[LO(tmp) + d];
+        s[LO(Mgrad) + d] = mg;
+        vreal sn = -mg + beta * s[LO(search) + d];
+        vreal mn = -s[LO(grad) + d] + beta * s[LO(mv) + d];
+        VNL_OPAQUE(sn);
+        VNL_OPAQUE(mn);  // (the stored values, see the first loop)
+        s[LO(search) + d] = sn;
+        s[LO(mv) + d] = mn;
+        ss += sn * sn;
+        if (qg_carried) {  // (the next iteration's, see above)
+          qg1c += sn * s[LO(Ma) + d] - sn * s[LO(smooth) + d];
+          qg2c += sn * mn;
+        }
+      }
+#endif
       ss = vnl_wave_sum(ss);
+      if (qg_carried) qg1c = vnl_wave_sum(qg1c), qg2c = vreal(0.5) * vnl_wave_sum(qg2c);
       VNL_SYNC();
       if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
       VNL_PROF(25);
