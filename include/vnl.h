@@ -12,6 +12,7 @@
  *   vnl_policy_*   <->  make_inference_fn(...).policy reference ppo_imitation/ppo_networks.py:45-83
  *                       IntentionNetwork.__call__     reference ppo_imitation/intention_policy_network.py:91-105
  *   vnl_rollout_post <-> brax Episode/AutoReset wrappers (train.py:204-214) + Transition of actor_step (acting.py:34-57)
+ *   vnl_env_step_post <-> vnl_env_step and vnl_rollout_post in ONE launch: each step wave post-processes its own env
  *   vnl_gather_rows / vnl_ppo_head / vnl_adam_step
  *                  <->  the minibatch gather, loss head (intention_losses.py:26-87,131-202) and optimiser update of one
  *                       PPO minibatch step (ppo_imitation/train.py:231-291)
@@ -345,6 +346,14 @@ typedef struct vnl_post_desc {
   vnl_post_op ops[VNL_POST_MAX_OPS];
 } vnl_post_desc;
 int vnl_rollout_post(const vnl_post_desc*, int32_t num_envs, void* stream);
+/* vnl_env_step followed by vnl_rollout_post(desc, num_envs = the env's own), as ONE launch: the wave that has stepped env e
+ * runs the post-processing of env e as its epilogue, while the other resident waves are still in their physics -- no launch
+ * that waits for the last step wave, none that the next policy launch waits for.  Same per-env semantics and order as
+ * above, the same words in every buffer; the descriptor is validated as by vnl_rollout_post (same codes, same messages)
+ * and copied into the launch's arguments (capturable in a hipGraph; it need not outlive the call).  The rows of an op move
+ * in batches -- the loads of several ops before their stores -- so an op's src / first row must not be ANOTHER op's dst
+ * or log row (dst == src of one op is fine).  For envs with a domain the randomised kernels take the same entry. */
+int vnl_env_step_post(vnl_env*, const float* action, const vnl_state* state, const vnl_post_desc* desc, void* stream);
 
 /* ---- PPO loss head: everything of compute_ppo_intention_loss after the network forward passes ----
  * (reference ppo_imitation/intention_losses.py:26-87 compute_gae, :131-202 loss) in three small launches: GAE,

@@ -24,13 +24,13 @@ int vnl_domain_reset_(const KernelConsts* kc, int spec, int B, size_t lds, void*
 }
 
 int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const vreal* action,
-                     vreal* dump, vreal* dump_mid, int* trace) {
+                     vreal* dump, vreal* dump_mid, int* trace, const vnl_post_desc& post) {
   if (spec)
     hipLaunchKernelGGL((vnl_step_kernel<VnlSpecDom<VnlSpecRodent>>), dim3(B), dim3(64), lds, (hipStream_t)stream, kc, ds,
-                       action, dump, dump_mid, trace);
+                       action, dump, dump_mid, trace, post);
   else
     hipLaunchKernelGGL((vnl_step_kernel<VnlSpecDom<VnlSpecGeneric>>), dim3(B), dim3(64), lds, (hipStream_t)stream, kc, ds,
-                       action, dump, dump_mid, trace);
+                       action, dump, dump_mid, trace, post);
   return (int)hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // The env kernels (one env per 64-lane workgroup) as templates over the compile-time model SP: instantiated for the shared
 // model in vnl_lib.hip, for per-env parameter tables (VnlSpecDom) in vnl_domain.hip.
 #pragma once
+#include "../../include/vnl.h"
 #include "vnl_body.h"
 
 // (VNL_KERNEL_ATTR: empty in the product; csrc/build.py --spill sets a VGPR cap to force register spills to scratch,
@@ -12,16 +13,101 @@
 #endif
 #define VNL_ENV_KERNEL __launch_bounds__(64) VNL_KERNEL_ATTR
 
+// The rollout post-processing of ONE env (include/vnl.h above vnl_post_desc: the same decisions and the same word copies as
+// vnl_post_kernel of vnl_lib.hip) by the wave that has just stepped that env: the step kernel's epilogue (vnl_env_step_post).
+// A finished wave's copies run under the physics of the other resident waves instead of in a launch of their own that can
+// only start when the last step wave has ended.
+// One wave must not pay a round trip per op: the ops are flattened into (op, trip of VNL_LANES words) items, and the loads of
+// VNL_POST_BATCH items are requested back to back before the first of their stores (value and the two store addresses of a
+// slot stay in registers; a null address = nothing to store for this lane).  The loads of a batch come before its stores:
+// an op's `src` / `first` row must not be another op's `dst` / `log` row (dst == src of the SAME op is fine).
+// The descriptor is a by-value kernel argument that only this function reads (scalar loads from the kernel-argument
+// segment, an op's ten words when the cursor enters it).
+#define VNL_POST_BATCH 16
+#ifdef VNL_FORKJOIN_DEFINED /* the host simulation */
+#define VNL_POST_LANDED(x)
+#else
+#define VNL_POST_LANDED(x) asm volatile("" : "+v"(x))
+#endif
+VNL_HD void vnl_post_epilogue(const vnl_post_desc& d, const unsigned e, const unsigned lane) {
+  VNL_SYNC_GLOBAL();  // (done, reward, obs, the state and info rows: stored by other lanes of this wave)
+  // every lane evaluates the decision itself from the OLD values, which must have returned before lane 0 stores the new ones;
+  // the four loads are requested together (an absent row reads `done` in its place and is not used): one round trip, not four
+  const float old_prev = (d.prev_done ? d.prev_done : d.done)[e], old_steps = (d.steps ? d.steps : d.done)[e];
+  const float rew = (d.reward ? d.reward : d.done)[e];
+  float done = d.done[e];
+  float st = d.steps ? ((d.prev_done && old_prev != 0.f) ? 0.f : old_steps) + (float)d.action_repeat : 0.f;
+  bool over = d.steps && st >= (float)d.episode_length;
+  float trunc = over ? 1.f - done : 0.f;
+  done = over ? 1.f : done;
+  VNL_SYNC_GLOBAL();
+  VNL_SERIAL {
+    if (d.steps) d.steps[e] = st;
+    if (d.prev_done) d.prev_done[e] = done;
+    d.done[e] = done;
+    if (d.truncation) d.truncation[e] = trunc;
+    if (d.log_reward) d.log_reward[e] = rew;
+    if (d.log_discount) d.log_discount[e] = 1.f - done;
+    if (d.log_truncation) d.log_truncation[e] = trunc;
+  }
+  const bool reset = done != 0.f;
+  const int n = d.num_ops;
+  int k = 0, base = 0;  // the cursor: op, first word of its next trip (wave-uniform)
+  const unsigned* src = nullptr;
+  unsigned *dst = nullptr, *log = nullptr;
+  int width = 0;
+  while (k < n) {
+    unsigned v[VNL_POST_BATCH];
+    unsigned *pd[VNL_POST_BATCH], *pl[VNL_POST_BATCH];
+#pragma unroll
+    for (int j = 0; j < VNL_POST_BATCH; j++) {
+      pd[j] = pl[j] = nullptr;
+      v[j] = 0u;
+      if (k < n) {
+        if (base == 0) {  // (all ten words of the op are requested at once: selects, no branch between its fields)
+          const float *o_src = d.ops[k].src, *o_first = d.ops[k].first;
+          float *o_dst = d.ops[k].dst, *o_log = d.ops[k].log;
+          width = d.ops[k].width;
+          const bool from_first = o_first && reset;
+          const size_t row = (size_t)e * width;
+          src = (const unsigned*)(from_first ? o_first : o_src) + row;
+          dst = (o_dst && (from_first || (const float*)o_dst != o_src)) ? (unsigned*)o_dst + row : nullptr;
+          log = o_log ? (unsigned*)o_log + row : nullptr;
+        }
+        const int i = base + (int)lane;
+        if (i < width) {
+          v[j] = src[i];
+          pd[j] = dst ? dst + i : nullptr;
+          pl[j] = log ? log + i : nullptr;
+        }
+        base += VNL_LANES;
+        if (base >= width) k++, base = 0;
+      }
+    }
+    // (the whole batch has landed before its first store: one wait here, none between the stores -- a wait inside a
+    // store's own branch would have to cover the stores before it as well, which share the loads' counter)
+#pragma unroll
+    for (int j = 0; j < VNL_POST_BATCH; j++) VNL_POST_LANDED(v[j]);
+#pragma unroll
+    for (int j = 0; j < VNL_POST_BATCH; j++) {
+      if (pd[j]) *pd[j] = v[j];
+      if (pl[j]) *pl[j] = v[j];
+    }
+  }
+}
+
 // One env per 64-lane workgroup; the env's whole working set lives in dynamic LDS (~25 KB ->
-// 6 workgroups per CU, 1536 envs in flight on 256 CUs).
+// 6 workgroups per CU, 1536 envs in flight on 256 CUs).  `post`: the rollout post-processing of this env as the wave's
+// epilogue (vnl_env_step_post), or num_ops < 0: none (vnl_env_step).
 template <class SP>
 __global__ void VNL_ENV_KERNEL vnl_step_kernel(const KernelConsts* kc, DevState st, const vreal* action,
-                                                      vreal* dump, vreal* dump_mid, int* trace) {
+                                                      vreal* dump, vreal* dump_mid, int* trace, vnl_post_desc post) {
   VNL_LDS_DECL(lds);
   const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
   EnvWaveT<SP> w{k->m, k->ev, st, k->L, lds, blockIdx.x, threadIdx.x, k, nullptr};
   w.step(action, dump_mid, trace);
   if (dump) w.dump(dump);
+  if (post.num_ops >= 0) vnl_post_epilogue(post, blockIdx.x, threadIdx.x);
 }
 
 template <class SP>

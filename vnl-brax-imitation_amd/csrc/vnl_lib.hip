@@ -1075,7 +1075,7 @@ __global__ void __launch_bounds__(64) vnl_fk_kernel(const KernelConsts* kc, DevS
 int vnl_domain_reset_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const int* start_frame,
                       const vreal* noise, vreal* dump, int* trace);
 int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const vreal* action,
-                     vreal* dump, vreal* dump_mid, int* trace);
+                     vreal* dump, vreal* dump_mid, int* trace, const vnl_post_desc& post);
 int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds,
                            const ResetDoneArgs& a, vreal* dump, int* trace);
 
@@ -1177,29 +1177,56 @@ extern "C" int vnl_env_fk(vnl_env* env, const float* qpos, const vnl_state* stat
   return VNL_OK;
 }
 
-extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* state, void* stream) {
-  if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step: null argument");
+// (vnl_rollout_post and vnl_env_step_post: one validation, one set of messages)
+static int post_desc_check(const vnl_post_desc* desc, int32_t num_envs) {
+  if (!desc || num_envs <= 0 || !desc->done) return fail(VNL_ERR_ARG, "vnl_rollout_post: null argument");
+  if (desc->num_ops < 0 || desc->num_ops > VNL_POST_MAX_OPS) return fail(VNL_ERR_ARG, "vnl_rollout_post: too many ops");
+  for (int k = 0; k < desc->num_ops; k++)
+    if (!desc->ops[k].src || desc->ops[k].width <= 0) return fail(VNL_ERR_ARG, "vnl_rollout_post: bad op");
+  if ((desc->log_reward && !desc->reward)) return fail(VNL_ERR_ARG, "vnl_rollout_post: log_reward without reward");
+  return VNL_OK;
+}
+
+// `post`: the descriptor the step waves run as their epilogue, or null (num_ops < 0 in the kernel: no epilogue)
+static int env_step_launch(vnl_env* env, const float* action, const vnl_state* state, const vnl_post_desc* post, void* stream) {
   DevState ds;
   int rc = to_dev_state(state, &ds);
   if (rc != VNL_OK) return rc;
   DeviceGuard guard(env->device);
   if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+  vnl_post_desc none{};
+  none.num_ops = -1;
+  const vnl_post_desc& pd = post ? *post : none;
   if (env->has_dom) {
     HIPCHK((hipError_t)vnl_domain_step_(env->kc, env->spec, env->B, env->lds_bytes, stream, ds, (const vreal*)action,
                                         env->debug == 1 ? env->dump : nullptr, env->debug == 2 ? env->dump : nullptr,
-                                        env->debug ? env->trace : nullptr));
+                                        env->debug ? env->trace : nullptr, pd));
     return VNL_OK;
   }
   if (env->spec)
     hipLaunchKernelGGL((vnl_step_kernel<VnlSpecRodent>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
                        (const KernelConsts*)env->kc, ds, (const vreal*)action, env->debug == 1 ? env->dump : nullptr,
-                       env->debug == 2 ? env->dump : nullptr, env->debug ? env->trace : nullptr);
+                       env->debug == 2 ? env->dump : nullptr, env->debug ? env->trace : nullptr, pd);
   else
     hipLaunchKernelGGL((vnl_step_kernel<VnlSpecGeneric>), dim3(env->B), dim3(64), env->lds_bytes, (hipStream_t)stream,
                        (const KernelConsts*)env->kc, ds, (const vreal*)action, env->debug == 1 ? env->dump : nullptr,
-                       env->debug == 2 ? env->dump : nullptr, env->debug ? env->trace : nullptr);
+                       env->debug == 2 ? env->dump : nullptr, env->debug ? env->trace : nullptr, pd);
   HIPCHK(hipGetLastError());
   return VNL_OK;
+}
+
+extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* state, void* stream) {
+  if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step: null argument");
+  return env_step_launch(env, action, state, nullptr, stream);
+}
+
+// The step with vnl_rollout_post(desc, num_envs = the env's B) as the epilogue of each step wave (include/vnl.h)
+extern "C" int vnl_env_step_post(vnl_env* env, const float* action, const vnl_state* state, const vnl_post_desc* desc,
+                                 void* stream) {
+  if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step_post: null argument");
+  int rc = post_desc_check(desc, env->B);
+  if (rc != VNL_OK) return rc;
+  return env_step_launch(env, action, state, desc, stream);
 }
 
 // Domain randomisation (brax / MJX semantics: raw fields are replaced, the derived constants -- dof / body invweight0,
@@ -1494,11 +1521,8 @@ __global__ void __launch_bounds__(VNL_POST_THREADS) vnl_post_kernel(vnl_post_des
 }
 
 extern "C" int vnl_rollout_post(const vnl_post_desc* desc, int32_t num_envs, void* stream) {
-  if (!desc || num_envs <= 0 || !desc->done) return fail(VNL_ERR_ARG, "vnl_rollout_post: null argument");
-  if (desc->num_ops < 0 || desc->num_ops > VNL_POST_MAX_OPS) return fail(VNL_ERR_ARG, "vnl_rollout_post: too many ops");
-  for (int k = 0; k < desc->num_ops; k++)
-    if (!desc->ops[k].src || desc->ops[k].width <= 0) return fail(VNL_ERR_ARG, "vnl_rollout_post: bad op");
-  if ((desc->log_reward && !desc->reward)) return fail(VNL_ERR_ARG, "vnl_rollout_post: log_reward without reward");
+  int rc = post_desc_check(desc, num_envs);
+  if (rc != VNL_OK) return rc;
   hipLaunchKernelGGL(vnl_post_kernel, dim3(num_envs), dim3(VNL_POST_THREADS), 0, (hipStream_t)stream, *desc);
   HIPCHK(hipGetLastError());
   return VNL_OK;

@@ -465,7 +465,13 @@ class RodentTracking(Env):
         ev = getattr(self, "kernel_events", None)  # (start, end) torch.cuda.Event pair, used by bench.py
         if ev is not None:
             ev[0].record()
-        _lib.check(self._L, self._L.vnl_env_step(self._env_h, a.data_ptr(), C.byref(p), self._stream()))
+        # one-shot hand-over from the fused unroll (acting._generate_unroll_fused): the rollout post-processing of this step
+        # runs as the step kernel's epilogue (vnl_env_step_post) -- inside the launch the events time
+        post, self._post_desc = getattr(self, "_post_desc", None), None
+        if post is not None:
+            _lib.check(self._L, self._L.vnl_env_step_post(self._env_h, a.data_ptr(), C.byref(p), C.byref(post), self._stream()))
+        else:
+            _lib.check(self._L, self._L.vnl_env_step(self._env_h, a.data_ptr(), C.byref(p), self._stream()))
         if ev is not None:
             ev[1].record()
         self._hold = (a,)

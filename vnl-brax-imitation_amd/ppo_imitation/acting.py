@@ -67,12 +67,20 @@ def _device_noise(policy) -> bool:
 # which writes action / raw_action / log_prob / rand_log_prob / logits there itself; False = the policy allocates its outputs
 # and vnl_rollout_post copies them into the log, as on the generator path.
 _DIRECT_LOG = True
+# Private switch (tests compare the two): the wrappers and the Transition logging of a step run as the EPILOGUE of the env
+# step kernel (vnl_env_step_post: each wave post-processes the env it has just stepped); False = two launches,
+# vnl_env_step + vnl_rollout_post.  A library without the entry, or an env whose `step` does more than launch the kernel
+# (AntTracking), takes the two launches.
+_POST_EPILOGUE = True
 
 
 def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int, extra_fields) -> Tuple[State, Transition]:
-    """Same results as the generic loop below (tests compare the two), 2 launches per step besides the
-    policy: the env step kernel and vnl_rollout_post (which also writes the Transition's observation row).  With
-    AutoResetWrapper(mode="fresh") a third one, vnl_env_reset_done, starts the new episodes and writes the rows the reset
+    """Same results as the generic loop below (tests compare the two), 1 launch per step besides the
+    policy: the env step kernel, whose waves run the post-processing of vnl_rollout_post (which also writes the
+    Transition's observation row) as their epilogue (vnl_env_step_post; `_POST_EPILOGUE = False`: a launch of its own).  The
+    step's descriptor reaches the kernel through `base.step`: a one-shot attribute of the env object, so that a hook around
+    `base.step(state, action)` (bench.py's kernel events) sees the same call.  With
+    AutoResetWrapper(mode="fresh") a further launch, vnl_env_reset_done, starts the new episodes and writes the rows the reset
     changes (next_observation, the logged info fields); its draws are keyed by info["reset_step"] + t.
 
     With a device-noise policy step t draws at `policy.counter + t` and the counter advances by T once, after the loop (one
@@ -126,6 +134,10 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
     act_log = None
     dev_noise = _device_noise(policy)
     direct = dev_noise and _DIRECT_LOG
+    # (only where `step` IS the kernel launch: an env that works on the state after it -- AntTracking assembles its
+    # observation there -- must be post-processed after that work, i.e. by the launch of its own)
+    from ..envs.rodent import RodentTracking
+    epilogue = _POST_EPILOGUE and hasattr(base._L, "vnl_env_step_post") and type(base).step is RodentTracking.step
     if direct:  # the policy writes row t of the log itself (contiguous [B, w] slices); the env step reads its action there
         na = base.action_size
         f32 = lambda *shape: torch.empty((T, *shape), dtype=torch.float32, device=dev)  # noqa: E731
@@ -140,7 +152,8 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
             actions, pex = policy(info["traj"], st.obs, None, step_offset=t, advance=False)
         else:
             actions, pex = policy(info["traj"], st.obs, key)
-        base.step(st, actions)
+        if not epilogue:
+            base.step(st, actions)
         if px_log is None:
             act_log = new(*actions.shape, like=actions)
             px_log = {k2: new(*v.shape, like=v) for k2, v in pex.items()}
@@ -157,7 +170,14 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
             keep.append(src)
         d.log_reward, d.log_discount = ptr(rew_log[t]), ptr(disc_log[t])
         d.log_truncation = ptr(sx_log["truncation"][t]) if "truncation" in sx_log else C.c_void_p(0)
-        _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
+        if epilogue:  # (the descriptor is copied into the launch's arguments by the call)
+            base._post_desc = d
+            try:
+                base.step(st, actions)
+            finally:
+                base._post_desc = None
+        else:
+            _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
         _generate_unroll_fused.hold = keep  # the launch is asynchronous: keep this step's sources alive
         if fresh:
             base.reset_done(st, st.done, seed=ar.seed, step_base=info["reset_step"], step_offset=t, env_offset=ar.env_offset,
