@@ -207,6 +207,46 @@ typedef struct vnl_reset_log {
 int vnl_env_reset_done(vnl_env*, const float* mask /* [num_envs] float32 */, const vnl_reset_noise*, const vnl_state*,
                        const vnl_reset_log* logs, int32_t num_logs, void* stream);
 
+/* Prioritised start frames (opt-in): vnl_env_reset_done with the start frame and clip drawn from a TABLE and the episodes
+ * that end counted, so that a training loop can start more often where episodes fail.  A cell is clip * start_hi +
+ * start_frame; ncell = num_clips * start_hi, at most 32768 (frames are not binned into coarser cells).
+ * A null descriptor: vnl_env_reset_done exactly (which IS this entry called with a null descriptor).
+ * Counting -- for an env whose mask is set, BEFORE anything of it is overwritten: sf0 = cur_frame - sub_clip_frame is the
+ *   finished episode's start frame, c0 = clip_id its clip.  If 0 <= sf0 < start_hi, 0 <= c0 < num_clips and truncation is
+ *   null or truncation[e] == 0: ended[c0 * start_hi + sf0] += 1, and failed[..] += 1 if also sub_clip_frame <
+ *   sub_clip_length (it ended before its sub-clip did).  Anything out of range is skipped, never indexed.  Integer atomic
+ *   adds: the counts do not depend on the order.  Unmasked envs count nothing; with `ended` and `failed` null nothing is
+ *   counted.
+ * Draw -- word x0 of block 0x80000000 of stream 3 (the block of the uniform draws; x1 is unused):
+ *   cell = #{ c < ncell - 1 : cdf[c] <= x0 }, start_frame = cell % start_hi, clip_id = cell / start_hi.
+ *   cdf is nondecreasing; cell c owns the words [cdf[c - 1], cdf[c]) (cdf[-1] = 0), the last cell the rest: entry
+ *   ncell - 1 is never read, and a cell of width 0 is never drawn.  The noise blocks are untouched: a weighted reset has
+ *   the noise bits of the uniform one.  The rest is the reset of vnl_env_reset_done on the stored draws.
+ *   ppo_imitation/philox.py (weighted_cells) restates the draw in torch ops.
+ * Beyond vnl_env_reset_done's checks, with nothing launched: VNL_ERR_ARG for a null cdf, ncell != num_clips * start_hi, or
+ * exactly one of ended / failed null; VNL_ERR_UNSUPPORTED for ncell > 32768. */
+typedef struct vnl_start_priority {
+  const uint32_t* cdf;      /* device [ncell], ncell = num_clips * start_hi */
+  int32_t ncell, pad_;
+  uint32_t *ended, *failed; /* device [ncell] each, or both null: no counting */
+  const float* truncation;  /* device [num_envs] or null */
+} vnl_start_priority;
+int vnl_env_reset_done_weighted(vnl_env*, const float* mask, const vnl_reset_noise*, const vnl_start_priority*,
+                                const vnl_state*, const vnl_reset_log*, int32_t num_logs, void* stream);
+
+/* Counters -> table, in one launch of one workgroup, all in integers (exact, independent of any order).  With a = prior:
+ *   n = min(ended[c], 2^20), f = min(failed[c], n)
+ *   s = ((f + a) << 16) / (n + 2 a)      64-bit; the smoothed failure rate in Q16, at most 65535
+ *   t = s + floor_q16                    the uniform floor: a cell that never fails keeps weight
+ *   P_c = t_0 + .. + t_c (64-bit), S = P_{ncell-1} < 2^32
+ *   cdf[c] = (P_c << 32) / S for c < ncell - 1, cdf[ncell - 1] = 0xFFFFFFFF
+ * then ended[c] >>= decay_shift, failed[c] >>= decay_shift (0 keeps accumulating).  Every cell's width is at least 1: no
+ * cell becomes unreachable.  Zero counters give the uniform table cdf[c] = ((c + 1) << 32) / ncell.
+ * ppo_imitation/philox.py (start_priority_table) restates it.  VNL_ERR_ARG, with nothing launched, for a null pointer,
+ * ncell < 1, prior < 1, floor_q16 outside 1..65536 or decay_shift outside 0..31; VNL_ERR_UNSUPPORTED for ncell > 32768. */
+int vnl_start_priority_update(uint32_t* ended, uint32_t* failed, uint32_t* cdf, int32_t ncell, uint32_t prior,
+                              uint32_t floor_q16, int32_t decay_shift, void* stream);
+
 /* step: action [num_envs][nu]; state updated in place. */
 int vnl_env_step(vnl_env*, const float* action, const vnl_state* state, void* stream);
 /* Forward kinematics only (reference preprocessing/mjx_preprocess.py:85-107: `mjx.kinematics` scanned over the frames of a

@@ -14,6 +14,11 @@ envs it reset, and then the launch alone with 0, 1/64, 1/8 and all of the envs m
 workgroups from the reset envs' forward pass.
 
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/fresh_reset_bench.py --rounds 1 --mode fresh
+
+--start-priority: the legs are fresh mode without and with a StartPriority (envs/start_priority.py: start frame and clip
+drawn from a table by a wave-wide search, the ended episodes counted by atomics; `update()` after every replay, as train()
+runs it after every unroll), alternated in this one process; and the update kernel alone at 15,040 cells (64 clips x 235
+frames; median of 20 launches between event pairs).
 """
 from __future__ import annotations
 
@@ -36,6 +41,9 @@ def resource_lines() -> dict:
     if os.path.exists(path):
         for line in open(path):
             name, _, rest = line.strip().partition(" ")
+            if "vnl_priority_kernel" in name:
+                kv = dict(re.findall(r"(\S[^=]*?)=(-?\d+)(?=\s|$)", rest))
+                out["vnl_priority_kernel"] = {k: int(v) for k, v in kv.items() if k in keep}
             if "vnl_reset_done_kernel" in name:
                 kv = dict(re.findall(r"(\S[^=]*?)=(-?\d+)(?=\s|$)", rest))
                 out[re.sub(r"^_Z\d+vnl_reset_done_kernelI|EvPK.*$", "", name)] = {k: int(v) for k, v in kv.items() if k in keep}
@@ -51,6 +59,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mode", choices=("both", "first_state", "fresh"), default="both")
     ap.add_argument("--per-step", action="store_true", help="also time every control step of one eager fused unroll in fresh mode")
+    ap.add_argument("--start-priority", action="store_true", help="legs: fresh mode without and with a StartPriority")
     args = ap.parse_args()
 
     import numpy as np
@@ -64,12 +73,21 @@ def main() -> None:
     dev = torch.device("cuda:0")
     B, T = args.envs, args.unroll
     modes = ("first_state", "fresh") if args.mode == "both" else (args.mode,)
+    if args.start_priority:
+        modes = ("fresh", "fresh_priority")
+    priorities = {}
 
     def setup(mode):
         base = RodentTracking(H.reference_clip(), num_envs=B, device=dev, **H.env_kwargs())
         ep = EpisodeWrapper(base, episode_length=150, action_repeat=1)
         # (the default mode is constructed as before the keyword existed: this file also runs against an older library)
-        env = AutoResetWrapper(ep) if mode == "first_state" else AutoResetWrapper(ep, mode="fresh", seed=7)
+        if mode == "fresh_priority":
+            from vnl_brax_imitation_amd.envs.start_priority import StartPriority
+
+            priorities[mode] = StartPriority(base)
+            env = AutoResetWrapper(ep, mode="fresh", seed=7, start_priority=priorities[mode])
+        else:
+            env = AutoResetWrapper(ep) if mode == "first_state" else AutoResetWrapper(ep, mode="fresh", seed=7)
         nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
                                                         preprocess_observations_fn=running_statistics.normalize,
                                                         intention_latent_size=64, encoder_layer_sizes=(256, 128),
@@ -87,15 +105,19 @@ def main() -> None:
     done_share = {m: [] for m in modes}
 
     def time_replays(mode) -> float:
-        g = unrolls[mode]
+        g, prio = unrolls[mode], priorities.get(mode)
         for _ in range(args.warmup):
             g()
+            if prio is not None:
+                prio.update()
         torch.cuda.synchronize(dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         share = torch.zeros((), device=dev)
         e0.record()
         for _ in range(args.replays):
             state, data = g()
+            if prio is not None:
+                prio.update()
         e1.record()
         share += (1 - data.discount).mean()  # (outside the timed span) the share of envs that finished per step, last replay
         torch.cuda.synchronize(dev)
@@ -112,8 +134,31 @@ def main() -> None:
            "spread_ms": {m: round(max(v) - min(v), 5) for m, v in ms.items()},
            "ms_all_rounds": {m: [round(x, 5) for x in v] for m, v in ms.items()},
            "share_of_envs_reset_per_step": {m: round(float(np.mean(v)), 5) for m, v in done_share.items()}}
-    if len(modes) == 2:
-        med = out["ms_per_control_step"]
+    med = out["ms_per_control_step"]
+    if args.start_priority:
+        out["priority_minus_fresh_ms"] = round(med["fresh_priority"] - med["fresh"], 5)
+        prio = priorities["fresh_priority"]
+        out["episodes_counted_in_window"] = int(prio.ended.sum())
+        out["largest_cell_probability_times_ncell"] = round(float(prio.probabilities().max()) * prio.ncell, 3)
+        # the update kernel alone at 64 clips x 235 frames
+        from vnl_brax_imitation_amd import _lib
+
+        L, n = _lib.load_library(), 64 * 235
+        gen = torch.Generator(device=dev).manual_seed(3)
+        ended = torch.randint(0, 1000, (n,), generator=gen, device=dev, dtype=torch.int32)
+        failed = (ended.float() * torch.rand(n, generator=gen, device=dev)).to(torch.int32)
+        cdf = torch.zeros_like(ended)
+        us = []
+        for k in range(23):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(L, L.vnl_start_priority_update(ended.data_ptr(), failed.data_ptr(), cdf.data_ptr(), n, 1, 6554, 0,
+                                                      torch.cuda.current_stream(dev).cuda_stream))
+            e1.record()
+            torch.cuda.synchronize(dev)
+            us.append(e0.elapsed_time(e1) * 1e3)
+        out["update_kernel_us_at_15040_cells"] = round(float(np.median(us[3:])), 1)
+    elif len(modes) == 2:
         out["fresh_minus_first_state_ms"] = round(med["fresh"] - med["first_state"], 5)
     if args.per_step and "fresh" in modes:
         # where the time goes: one eager fused unroll, an event pair around the reset launch of every step -- steps on which

@@ -99,6 +99,13 @@ class ResetLog(C.Structure):  # include/vnl.h: vnl_reset_log
     _fields_ = [("src", C.c_void_p), ("log", C.c_void_p), ("width", C.c_int32), ("pad_", C.c_int32)]
 
 
+class StartPriorityDesc(C.Structure):  # include/vnl.h: vnl_start_priority
+    _fields_ = [("cdf", C.c_void_p), ("ncell", C.c_int32), ("pad_", C.c_int32), ("ended", C.c_void_p), ("failed", C.c_void_p),
+                ("truncation", C.c_void_p)]
+
+
+PRIORITY_MAX_CELLS = 32768
+
 POST_MAX_OPS = 24
 
 
@@ -166,7 +173,7 @@ class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device
 
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
-    "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_step", "vnl_env_step_post", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
+    "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_reset_done_weighted", "vnl_start_priority_update", "vnl_env_step", "vnl_env_step_post", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
     "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
@@ -194,6 +201,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.vnl_env_dims.argtypes = [vp, C.POINTER(Dims)]
     lib.vnl_env_reset.argtypes = [vp, vp, vp, C.POINTER(StatePtrs), vp]
     lib.vnl_env_reset_done.argtypes = [vp, vp, C.POINTER(ResetNoise), C.POINTER(StatePtrs), C.POINTER(ResetLog), C.c_int32, vp]
+    lib.vnl_env_reset_done_weighted.argtypes = [vp, vp, C.POINTER(ResetNoise), C.POINTER(StartPriorityDesc), C.POINTER(StatePtrs),
+                                                C.POINTER(ResetLog), C.c_int32, vp]
+    lib.vnl_start_priority_update.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, vp]
     lib.vnl_env_step.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     if hasattr(lib, "vnl_env_step_post"):
         lib.vnl_env_step_post.argtypes = [vp, vp, C.POINTER(StatePtrs), C.POINTER(PostDesc), vp]

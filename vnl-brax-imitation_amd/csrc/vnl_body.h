@@ -161,6 +161,42 @@ VNL_HD float vnl_recip(float x) {
 }
 #endif
 
+// ---- prioritised start frames (include/vnl.h: vnl_start_priority; EnvWaveT::reset_fresh) ----
+// vnl_count_add: one outcome into a cell's counter.  Many envs hit one cell: an integer vector atomic, so that the counts do
+// not depend on the order of the adds.
+// vnl_cdf_cell: #{ c < ncell - 1 : cdf[c] <= x } of a nondecreasing table, the same x in every lane.  A 64-ary search by the
+// whole wave instead of a chain of 15 dependent loads on one lane: in each round lane l loads the LAST entry of the l-th of 64
+// equal pieces of the undecided interval, the ballot's popcount k says that the first k pieces lie at or below x, and piece
+// k without its last entry is what stays undecided; the last round (at most 64 entries) loads them all and counts.  One
+// round for ncell <= 64, two for <= 4096, three for the 32768 cells the entry accepts.  No index leaves [0, ncell - 1),
+// whatever the table holds: entry ncell - 1 is never read.
+#ifndef VNL_FORKJOIN_DEFINED
+VNL_HD void vnl_count_add(uint32_t* p) { atomicAdd(p, 1u); }
+VNL_HD int vnl_cdf_cell(const uint32_t* cdf, int ncell, uint32_t x, unsigned lane) {
+  int lo = 0, len = ncell - 1;  // entries [lo, lo + len) are undecided; every entry before lo is <= x, every one behind > x
+  while (len > VNL_LANES) {
+    const int stride = (len + VNL_LANES - 1) / VNL_LANES, end = lo + len;
+    const int p = lo + ((int)lane + 1) * stride - 1;
+    const bool le = p < end && cdf[p] <= x;
+    const int k = (int)__popcll(__ballot(le));
+    lo = lo + k * stride < end ? lo + k * stride : end;
+    len = end - lo < stride - 1 ? end - lo : stride - 1;
+  }
+  const bool le = (int)lane < len && cdf[lo + (int)lane] <= x;
+  return lo + (int)__popcll(__ballot(le));
+}
+#else /* the host simulation: one lane per launch -- a plain add, a binary search */
+VNL_HD void vnl_count_add(uint32_t* p) { *p += 1u; }
+VNL_HD int vnl_cdf_cell(const uint32_t* cdf, int ncell, uint32_t x, unsigned) {
+  int lo = 0, hi = ncell - 1;  // the answer lies in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cdf[mid] <= x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+#endif
+
 // Diagnostic build only (-DVNL_PROFILE, csrc/build.py --profile): per-stage s_memtime stamps summed
 // into a __device__ array that no product code reads.  Never defined in the shipped library.
 #ifdef VNL_PROFILE
@@ -3013,6 +3049,37 @@ struct EnvWaveT {
   // bias under 2^-32 * start_hi (5.5e-8 for the reference's 235 start frames).
   // The draws go through memory -- the caller's record rows or library scratch -- and the reset body of vnl_env_reset then
   // runs on those rows: the arithmetic of a fresh reset IS that of vnl_env_reset given the recorded draws.
+  // The integer draws of reset_fresh from a table of start priorities (include/vnl.h: vnl_start_priority), and the outcome
+  // of the episode that has just ended counted into the cell it started in.  A cell is clip * start_hi + start_frame.
+  // Counting comes first, while cur_frame, sub_clip_frame and clip_id still are the finished episode's: its start frame is
+  // cur_frame - sub_clip_frame; it FAILED if it ended before its sub-clip did; a truncated episode (the wrapper's step
+  // limit, not the env's doing) and anything out of range count nothing.
+  // The draw: word x0 of the block the uniform draws use, cell = #{ c < ncell - 1 : cdf[c] <= x0 } (vnl_cdf_cell).  Every
+  // lane computes the block -- ten rounds of integer multiplies, cheaper than a broadcast through memory.
+  VNL_HD void reset_fresh_weighted(const ResetDoneArgs& a, uint32_t c1, uint32_t c2, uint32_t c3) const {
+    const int hi = (int)a.start_hi;
+    VNL_SERIAL {
+      if (a.prio.ended) {
+        const int sub = st.sub_clip_frame[e], c0 = st.clip_id[e];
+        const int64_t sf0 = (int64_t)st.cur_frame[e] - sub;
+        const bool truncated = a.prio.truncation && a.prio.truncation[e] != 0.f;
+        if (sf0 >= 0 && sf0 < hi && c0 >= 0 && c0 < ev.C && !truncated) {
+          const int cell = c0 * hi + (int)sf0;
+          vnl_count_add(a.prio.ended + cell);
+          if (sub < ev.sub_clip_length) vnl_count_add(a.prio.failed + cell);
+        }
+      }
+    }
+    uint32_t x[4];
+    philox4x32_10(0x80000000u, c1, c2, c3, a.key0, a.key1, x);
+    const int cell = vnl_cdf_cell(a.prio.cdf, a.prio.ncell, x[0], lane);
+    VNL_SERIAL {
+      const int clip = cell / hi;
+      a.start_frame[e] = cell - clip * hi;
+      a.clip_id[e] = clip, st.clip_id[e] = clip;
+    }
+  }
+
   VNL_HD void reset_fresh(const ResetDoneArgs& a, int* trace_base) const {
     const int nq = MI(nq), nblk = (nq + 3) >> 2;
     const int64_t step = *a.step_base + a.step_offset;
@@ -3027,12 +3094,16 @@ struct EnvWaveT {
       for (int q = 0; q < 4; q++)
         if (4 * b + q < nq) nz[4 * b + q] = vreal(v[q] * a.noise_scale);
     }
-    VNL_SERIAL {
-      uint32_t x[4];
-      philox4x32_10(0x80000000u, c1, c2, c3, a.key0, a.key1, x);
-      const int clip = (int)(((uint64_t)x[1] * (uint32_t)ev.C) >> 32);
-      a.start_frame[e] = (int)(((uint64_t)x[0] * a.start_hi) >> 32);
-      a.clip_id[e] = clip, st.clip_id[e] = clip;
+    if (a.prio.cdf) {
+      reset_fresh_weighted(a, c1, c2, c3);
+    } else {
+      VNL_SERIAL {
+        uint32_t x[4];
+        philox4x32_10(0x80000000u, c1, c2, c3, a.key0, a.key1, x);
+        const int clip = (int)(((uint64_t)x[1] * (uint32_t)ev.C) >> 32);
+        a.start_frame[e] = (int)(((uint64_t)x[0] * a.start_hi) >> 32);
+        a.clip_id[e] = clip, st.clip_id[e] = clip;
+      }
     }
     VNL_SYNC_GLOBAL();  // (every lane reads the start frame and clip that lane 0 stored, and the noise row)
     reset_core<true>(a.start_frame, a.noise, trace_base);

@@ -1121,8 +1121,11 @@ extern "C" int vnl_env_reset(vnl_env* env, const int32_t* start_frame, const flo
 }
 
 // A fresh episode, drawn in the kernel, for the envs whose mask is set (include/vnl.h; EnvWaveT::reset_fresh)
-extern "C" int vnl_env_reset_done(vnl_env* env, const float* mask, const vnl_reset_noise* noise, const vnl_state* state,
-                                  const vnl_reset_log* logs, int32_t num_logs, void* stream) {
+// .. with the start frame and clip drawn from a table of start priorities and the ended episodes counted (include/vnl.h:
+// vnl_start_priority; EnvWaveT::reset_fresh_weighted); a null `prio` = the uniform draws
+extern "C" int vnl_env_reset_done_weighted(vnl_env* env, const float* mask, const vnl_reset_noise* noise,
+                                           const vnl_start_priority* prio, const vnl_state* state, const vnl_reset_log* logs,
+                                           int32_t num_logs, void* stream) {
   if (!env || !mask || !noise || !state) return fail(VNL_ERR_ARG, "vnl_env_reset_done: null argument");
   if (!noise->step_base) return fail(VNL_ERR_ARG, "vnl_reset_noise: step_base is null (a device pointer to the step counter)");
   if (noise->start_hi < 1) return fail(VNL_ERR_ARG, "vnl_reset_noise: start_hi must be at least 1");
@@ -1137,7 +1140,18 @@ extern "C" int vnl_env_reset_done(vnl_env* env, const float* mask, const vnl_res
   DevState ds;
   int rc = to_dev_state(state, &ds);
   if (rc != VNL_OK) return rc;
+  if (prio) {
+    if (!prio->cdf) return fail(VNL_ERR_ARG, "vnl_start_priority: cdf is null");
+    if (prio->ncell > VNL_PRIORITY_MAX_CELLS) return fail(VNL_ERR_UNSUPPORTED, "vnl_start_priority: more than 32768 cells");
+    if ((int64_t)prio->ncell != (int64_t)env->de.C * noise->start_hi)
+      return fail(VNL_ERR_ARG, "vnl_start_priority: ncell must be num_clips * start_hi");
+    if (!prio->ended != !prio->failed) return fail(VNL_ERR_ARG, "vnl_start_priority: ended and failed go together");
+  }
   ResetDoneArgs a{};
+  if (prio) {
+    a.prio.cdf = prio->cdf, a.prio.ncell = prio->ncell, a.prio.ended = prio->ended, a.prio.failed = prio->failed;
+    a.prio.truncation = prio->truncation;
+  }
   a.mask = mask, a.step_base = noise->step_base, a.step_offset = noise->step_offset;
   a.key0 = (uint32_t)noise->seed, a.key1 = (uint32_t)(noise->seed >> 32), a.env0 = (uint32_t)noise->env_offset;
   a.start_hi = (uint32_t)noise->start_hi, a.noise_scale = noise->noise_scale, a.num_logs = num_logs;
@@ -1162,6 +1176,11 @@ extern "C" int vnl_env_reset_done(vnl_env* env, const float* mask, const vnl_res
                        (const KernelConsts*)env->kc, ds, a, dump, trace);
   HIPCHK(hipGetLastError());
   return VNL_OK;
+}
+
+extern "C" int vnl_env_reset_done(vnl_env* env, const float* mask, const vnl_reset_noise* noise, const vnl_state* state,
+                                  const vnl_reset_log* logs, int32_t num_logs, void* stream) {
+  return vnl_env_reset_done_weighted(env, mask, noise, nullptr, state, logs, num_logs, stream);
 }
 
 extern "C" int vnl_env_fk(vnl_env* env, const float* qpos, const vnl_state* state, void* stream) {
@@ -1795,6 +1814,75 @@ extern "C" int vnl_adam_step(float* params, const float* grads, float* mu, float
   hipLaunchKernelGGL(vnl_adam_kernel, dim3((unsigned)blocks), dim3(VNL_ADAM_THREADS), 0, (hipStream_t)stream, params,
                      grads, mu, nu, (const long long*)count, (long long)n, lr, b1, b2, eps);
   HIPCHK(hipGetLastError());
+  return VNL_OK;
+}
+
+// ---- start priorities (include/vnl.h: vnl_start_priority_update) -------------------------------------
+// Counters -> table, all in integers: the result is exact and does not depend on the order of any sum.
+// a cell's weight in Q16: its smoothed failure rate (f + a) / (n + 2 a) plus the uniform floor
+static __host__ __device__ inline uint32_t vnl_priority_weight(uint32_t ended, uint32_t failed, uint32_t prior, uint32_t floor_q16) {
+  const uint32_t n = ended < (1u << 20) ? ended : (1u << 20), f = failed < n ? failed : n;
+  return (uint32_t)((((uint64_t)f + prior) << 16) / ((uint64_t)n + 2ull * prior)) + floor_q16;
+}
+#ifndef VNL_FORKJOIN_DEFINED
+#define VNL_PRIORITY_THREADS 1024
+// One workgroup.  Thread t owns the contiguous cells [t chunk, (t + 1) chunk): it sums their weights, an inclusive scan
+// over the wave (shuffles) and over the waves' totals (LDS) turns the sums into 64-bit prefixes, and a second walk over the
+// chunk writes cdf[c] = (P_c << 32) / S and the decayed counters.  A thread reads its counters in both walks and writes
+// them at the end of the second: no other thread touches them.
+__global__ void __launch_bounds__(VNL_PRIORITY_THREADS) vnl_priority_kernel(uint32_t* ended, uint32_t* failed, uint32_t* cdf,
+                                                                            int ncell, uint32_t prior, uint32_t floor_q16,
+                                                                            int decay_shift) {
+  __shared__ unsigned long long wave_total[VNL_PRIORITY_THREADS / 64];
+  const int t = (int)threadIdx.x, chunk = (ncell + VNL_PRIORITY_THREADS - 1) / VNL_PRIORITY_THREADS;
+  const int c0 = t * chunk < ncell ? t * chunk : ncell, c1 = c0 + chunk < ncell ? c0 + chunk : ncell;
+  unsigned long long sum = 0ull;
+  for (int c = c0; c < c1; c++) sum += vnl_priority_weight(ended[c], failed[c], prior, floor_q16);
+  unsigned long long incl = sum;  // inclusive scan over the wave
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long up = __shfl_up(incl, d, 64);
+    if ((t & 63) >= d) incl += up;
+  }
+  if ((t & 63) == 63) wave_total[t >> 6] = incl;
+  __syncthreads();
+  unsigned long long before = 0ull, total = 0ull;
+  for (int w = 0; w < VNL_PRIORITY_THREADS / 64; w++) {
+    const unsigned long long v = wave_total[w];
+    before += w < (t >> 6) ? v : 0ull;
+    total += v;
+  }
+  unsigned long long run = before + incl - sum;  // the prefix in front of this thread's chunk
+  for (int c = c0; c < c1; c++) {
+    const uint32_t n = ended[c], f = failed[c];
+    run += vnl_priority_weight(n, f, prior, floor_q16);
+    cdf[c] = c == ncell - 1 ? 0xFFFFFFFFu : (uint32_t)((run << 32) / total);
+    ended[c] = n >> decay_shift, failed[c] = f >> decay_shift;
+  }
+}
+#endif
+
+// (in the host simulation a plain serial loop instead of the kernel: the CPU tier tests the arithmetic, the GPU tier the kernel)
+extern "C" int vnl_start_priority_update(uint32_t* ended, uint32_t* failed, uint32_t* cdf, int32_t ncell, uint32_t prior,
+                                         uint32_t floor_q16, int32_t decay_shift, void* stream) {
+  if (!ended || !failed || !cdf) return fail(VNL_ERR_ARG, "vnl_start_priority_update: null argument");
+  if (ncell < 1 || prior < 1) return fail(VNL_ERR_ARG, "vnl_start_priority_update: ncell and prior must be at least 1");
+  if (floor_q16 < 1 || floor_q16 > 65536 || decay_shift < 0 || decay_shift > 31)
+    return fail(VNL_ERR_ARG, "vnl_start_priority_update: floor_q16 must be 1..65536, decay_shift 0..31");
+  if (ncell > VNL_PRIORITY_MAX_CELLS) return fail(VNL_ERR_UNSUPPORTED, "vnl_start_priority_update: more than 32768 cells");
+#ifndef VNL_FORKJOIN_DEFINED
+  hipLaunchKernelGGL(vnl_priority_kernel, dim3(1), dim3(VNL_PRIORITY_THREADS), 0, (hipStream_t)stream, ended, failed, cdf,
+                     (int)ncell, prior, floor_q16, (int)decay_shift);
+  HIPCHK(hipGetLastError());
+#else
+  (void)stream;
+  uint64_t total = 0, run = 0;
+  for (int c = 0; c < ncell; c++) total += vnl_priority_weight(ended[c], failed[c], prior, floor_q16);
+  for (int c = 0; c < ncell; c++) {
+    run += vnl_priority_weight(ended[c], failed[c], prior, floor_q16);
+    cdf[c] = c == ncell - 1 ? 0xFFFFFFFFu : (uint32_t)((run << 32) / total);
+    ended[c] >>= decay_shift, failed[c] >>= decay_shift;
+  }
+#endif
   return VNL_OK;
 }
 

@@ -137,7 +137,15 @@ struct ResetDoneArgs {
     unsigned* log;
     int width, pad_;
   } logs[VNL_RESET_MAX_LOGS]; /* rows [num_envs][width] of 32-bit words */
+  /* prioritised start frames (include/vnl.h: vnl_start_priority); cdf null = the uniform draws of vnl_env_reset_done */
+  struct {
+    const uint32_t* cdf;      /* [ncell], cell = clip * start_hi + start_frame */
+    uint32_t *ended, *failed; /* [ncell] each, or both null */
+    const float* truncation;  /* [num_envs] or null */
+    int ncell, pad_;
+  } prio;
 };
+#define VNL_PRIORITY_MAX_CELLS 32768
 
 // per-env LDS sections (offsets in vreal elements)
 struct WsLayout {

@@ -414,14 +414,19 @@ class RodentTracking(Env):
         return max(self._clip_length - self._sub_clip_length - self._ref_traj_length, 1)
 
     def reset_done(self, state: State, mask: torch.Tensor, *, seed: int, step_base: torch.Tensor, step_offset: int = 0,
-                   env_offset: int = 0, logs=(), record: Optional[Dict[str, torch.Tensor]] = None) -> State:
+                   env_offset: int = 0, logs=(), record: Optional[Dict[str, torch.Tensor]] = None, priority=None,
+                   truncation: Optional[torch.Tensor] = None) -> State:
         """A fresh episode, in place, for the envs whose `mask` (B,) is nonzero (vnl_env_reset_done): start frame in
         [0, _start_hi()) -- the range of this env's own `reset` --, clip and reset noise drawn in the kernel from the counter-based
         stream keyed by (seed, step_base[0] + step_offset, env_offset + env index) -- ppo_imitation/philox.py reset_draws.
         reward, done and metrics keep the terminal step's values; nothing of an unmasked env changes.  `step_base`: int64 [1]
         on the env's device, only read (the caller advances it).  `logs`: up to 8 (src, log) pairs of (B[, w]) float32 /
         int32 tensors, log <- src for every env after the reset.  `record`: optional dict of int32 (B,) "start_frame",
-        "clip_id" and (B, nq) "noise" tensors that receive the draws of the reset envs."""
+        "clip_id" and (B, nq) "noise" tensors that receive the draws of the reset envs.
+        `priority` (envs/start_priority.py StartPriority, or any object with its tensors `cdf`, `count_ended`,
+        `count_failed`; the counters may be None): start frame and clip are drawn from its table instead -- philox.py
+        weighted_cells -- and the episodes that end here are counted into its counters (vnl_env_reset_done_weighted), except
+        those whose `truncation` (B,) float32 entry is nonzero."""
         B = self.num_envs
         if tuple(mask.shape) != (B,):
             raise ValueError(f"mask must be ({B},), got {tuple(mask.shape)}")
@@ -450,9 +455,29 @@ class RodentTracking(Env):
                 raise ValueError("a log is a (src, log) pair of contiguous float32 / int32 tensors of one shape (B[, w])")
             o.src, o.log, o.width = src.data_ptr(), log.data_ptr(), src.numel() // B
         p = self._ptrs(state)
-        _lib.check(self._L, self._L.vnl_env_reset_done(self._env_h, mk.data_ptr(), C.byref(nz), C.byref(p), arr, len(logs),
-                                                       self._stream()))
-        self._hold = (mk, step_base, logs, record)  # keep inputs alive until the stream has consumed them
+        if priority is None:
+            if truncation is not None:
+                raise ValueError("truncation has no meaning without a priority: nothing is counted")
+            _lib.check(self._L, self._L.vnl_env_reset_done(self._env_h, mk.data_ptr(), C.byref(nz), C.byref(p), arr, len(logs),
+                                                           self._stream()))
+        else:
+            pr = _lib.StartPriorityDesc()
+            words = [priority.cdf, priority.count_ended, priority.count_failed]
+            for t in words:
+                if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != self.device
+                                      or t.numel() != words[0].numel()):
+                    raise ValueError("a priority's cdf and counters are contiguous int32 (ncell,) tensors on the env's device")
+            pr.cdf, pr.ncell = priority.cdf.data_ptr(), priority.cdf.numel()
+            pr.ended = None if words[1] is None else words[1].data_ptr()
+            pr.failed = None if words[2] is None else words[2].data_ptr()
+            if truncation is not None:
+                if truncation.dtype != torch.float32 or tuple(truncation.shape) != (B,) or not truncation.is_contiguous() or \
+                        truncation.device != self.device:
+                    raise ValueError(f"truncation must be a contiguous float32 ({B},) tensor on the env's device")
+                pr.truncation = truncation.data_ptr()
+            _lib.check(self._L, self._L.vnl_env_reset_done_weighted(self._env_h, mk.data_ptr(), C.byref(nz), C.byref(pr), C.byref(p),
+                                                                    arr, len(logs), self._stream()))
+        self._hold = (mk, step_base, logs, record, priority, truncation)  # keep inputs alive until the stream has consumed them
         return state
 
     def step(self, state: State, action: torch.Tensor) -> State:

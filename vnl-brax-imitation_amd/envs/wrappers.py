@@ -89,10 +89,13 @@ class AutoResetWrapper(Wrapper):
     (`env.reset_done`, vnl_env_reset_done), keyed by (seed, info["reset_step"], env_offset + env index): no first state is
     cached, and the whole of `info` follows the reset.  `info["reset_step"]` is an int64[1] device counter that advances by
     one per step.  reward / done / metrics of the terminal step are kept, as under brax's auto-reset.
+    With `start_priority` (envs/start_priority.py StartPriority; mode="fresh" only) start frame and clip are drawn from its
+    table and the episodes that end are counted into its counters -- not those an EpisodeWrapper below truncated.  The
+    caller runs its `update()` (between unrolls).
     """
 
     def __init__(self, env: Env, reset_info_on_autoreset: bool = False, mode: str = "first_state", seed: int = 0,
-                 env_offset: int = 0):
+                 env_offset: int = 0, start_priority=None):
         super().__init__(env)
         if mode not in AUTO_RESET_MODES:
             raise ValueError(f"unknown auto-reset mode {mode!r}: expected one of {AUTO_RESET_MODES}")
@@ -100,7 +103,9 @@ class AutoResetWrapper(Wrapper):
             raise ValueError("reset_info_on_autoreset has no meaning with mode='fresh': a fresh reset rewrites the info")
         if mode == "fresh" and not hasattr(env.unwrapped, "reset_done"):
             raise ValueError(f"{type(env.unwrapped).__name__} has no reset_done: mode='fresh' needs a tracking env of this library")
-        self.reset_info = reset_info_on_autoreset
+        if start_priority is not None and mode != "fresh":
+            raise ValueError("start_priority needs mode='fresh': the cached first state has one start frame")
+        self.reset_info, self.start_priority = reset_info_on_autoreset, start_priority
         self.mode, self.seed, self.env_offset = mode, int(seed), int(env_offset)
 
     def reset(self, rng=None, **kw) -> State:
@@ -114,6 +119,12 @@ class AutoResetWrapper(Wrapper):
             state.info["first_info"] = {k: state.info[k].clone() for k in ("cur_frame", "sub_clip_frame", "traj")}
         return state
 
+    def priority_args(self, state: State) -> dict:
+        """the `priority` / `truncation` arguments of `reset_done` (none without a priority object)"""
+        if self.start_priority is None:
+            return {}
+        return {"priority": self.start_priority, "truncation": state.info.get("truncation")}
+
     def step(self, state: State, action: torch.Tensor) -> State:
         if "steps" in state.info:
             steps = state.info["steps"]
@@ -122,7 +133,8 @@ class AutoResetWrapper(Wrapper):
         state = self.env.step(state, action)
         if self.mode == "fresh":
             counter = state.info["reset_step"]
-            self.env.unwrapped.reset_done(state, state.done, seed=self.seed, step_base=counter, env_offset=self.env_offset)
+            self.env.unwrapped.reset_done(state, state.done, seed=self.seed, step_base=counter, env_offset=self.env_offset,
+                                          **self.priority_args(state))
             counter.add_(1)
             return state
         done = state.done.bool()
@@ -170,7 +182,7 @@ class EvalWrapper(Wrapper):
 
 def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None,
          reset_info_on_autoreset: bool = False, auto_reset: str = "first_state", auto_reset_seed: int = 0,
-         env_offset: int = 0) -> Wrapper:
+         env_offset: int = 0, start_priority=None) -> Wrapper:
     """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
 
     `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
@@ -180,7 +192,8 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
 
     `auto_reset`: "first_state" (brax: a done env returns to the cached first state) or "fresh" (a new start frame, clip
     and reset noise per episode, drawn on the device; AutoResetWrapper), with `auto_reset_seed` and `env_offset` (the global
-    index of this batch's env 0, for sharded runs) keying the draws."""
+    index of this batch's env 0, for sharded runs) keying the draws.  `start_priority`: with "fresh", a StartPriority
+    (envs/start_priority.py) whose table the draws follow and whose counters the resets feed."""
     if randomization_fn is not None:
         if not hasattr(env, "with_domain"):
             raise ValueError(f"{type(env).__name__} has no with_domain: domain randomisation needs a tracking env of this library")
@@ -193,4 +206,4 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
         if bodies:
             env = env.with_body_domain(bodies)
     return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset, mode=auto_reset,
-                            seed=auto_reset_seed, env_offset=env_offset)
+                            seed=auto_reset_seed, env_offset=env_offset, start_priority=start_priority)

@@ -115,6 +115,9 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
         # a done env starts a NEW episode (vnl_env_reset_done after the post launch, mask = the finalised done): nothing is
         # restored from a first state, and what the reset rewrites -- obs, the info fields -- is logged by that launch
         reset_logs = [(st.obs, nobs_log)] + [(info[x], sx_log[x]) for x in extra_fields if x != "truncation"]
+        # (a StartPriority of the wrapper's: the draws follow its table and the launch counts the ended episodes, those the
+        # post-processing has just marked as truncated excepted; the tensors are fixed for a captured graph's life)
+        prio_args = ar.priority_args(st)
     else:
         fps = info["first_pipeline_state"]
         for name in st.pipeline_state._FIELDS:
@@ -181,7 +184,7 @@ def _generate_unroll_fused(fz, env_state: State, policy, key, unroll_length: int
         _generate_unroll_fused.hold = keep  # the launch is asynchronous: keep this step's sources alive
         if fresh:
             base.reset_done(st, st.done, seed=ar.seed, step_base=info["reset_step"], step_offset=t, env_offset=ar.env_offset,
-                            logs=[(src, log[t]) for src, log in reset_logs])
+                            logs=[(src, log[t]) for src, log in reset_logs], **prio_args)
     if fresh:  # (like policy.counter: the launches carry offsets 0..T-1, one add per unroll -- a node of a captured graph)
         info["reset_step"].add_(T)
     if dev_noise:
@@ -222,6 +225,9 @@ class GraphedUnroll:
         # env state put back afterwards: building the graph must not consume randomness or advance the envs
         gen_state = policy.counter.clone() if dev_noise else key.get_state()
         saved = _snapshot_state(env_state)
+        prio = fz[0].start_priority  # (the warm-up's resets must not count either)
+        counters = [prio.count_ended, prio.count_failed] if prio is not None else []
+        saved_counters = [c.clone() for c in counters]
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -229,6 +235,8 @@ class GraphedUnroll:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         _restore_state(env_state, saved)
+        for c, s0 in zip(counters, saved_counters):
+            c.copy_(s0)
         self.graph = torch.cuda.CUDAGraph()
         if dev_noise:
             policy.counter.copy_(gen_state)

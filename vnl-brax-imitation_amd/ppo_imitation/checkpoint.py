@@ -9,6 +9,8 @@ brax.io.model pickles the pytree).  Here the same pair goes to one `.npz` (NumPy
     [value/params/<flax path>, optimizer/{mu,nu,count}, meta/env_steps]   full training state, for resume
     [meta/policy_counter]                the acting policy's noise step counter (train(policy_noise="device"))
     [meta/reset_step]                    the step counter of the fresh episode draws (train(auto_reset="fresh"))
+    [meta/start_priority_{cdf,ended,failed}]  table and counters of the prioritised start frames (train(start_priority=...)),
+                                         int32 words as envs/start_priority.py StartPriority.state_dict() gives them
 
 The tensor names are the reference's Flax tree (intention_policy_network.py:20-136), so a reference checkpoint
 converted to nested dicts of arrays maps 1:1 through `from_flax_tree` / `to_flax_tree`.
@@ -75,7 +77,8 @@ def _flatten(prefix: str, layout: ParamLayout, flat: torch.Tensor, out: Dict[str
 def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsState, torch.Tensor], ppo_network,
                 *, value_params: Optional[torch.Tensor] = None, optimizer_state: Optional[Dict[str, torch.Tensor]] = None,
                 env_steps: Optional[int] = None, policy_counter: Optional[torch.Tensor] = None,
-                reset_step: Optional[torch.Tensor] = None) -> str:
+                reset_step: Optional[torch.Tensor] = None,
+                start_priority: Optional[Dict[str, torch.Tensor]] = None) -> str:
     """`params` = the inference pair the reference saves; the keyword extras make the file resumable."""
     norm, policy = params
     out: Dict[str, np.ndarray] = {f"normalizer/{k}": getattr(norm, k).detach().cpu().numpy() for k in _NORM}
@@ -91,6 +94,9 @@ def save_params(path: str, params: Tuple[running_statistics.RunningStatisticsSta
         out["meta/policy_counter"] = policy_counter.detach().cpu().numpy().astype(np.int64).reshape(1)
     if reset_step is not None:
         out["meta/reset_step"] = reset_step.detach().cpu().numpy().astype(np.int64).reshape(1)
+    if start_priority is not None:
+        for k in ("cdf", "ended", "failed"):
+            out[f"meta/start_priority_{k}"] = start_priority[k].detach().cpu().numpy().astype(np.int32)
     if not path.endswith(".npz"):
         path += ".npz"
     np.savez(path, **out)
@@ -186,7 +192,8 @@ def convert_brax_params(pickle_path: str, ppo_network, npz_path: Optional[str] =
 
 
 def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
-    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps', 'policy_counter', 'reset_step'}."""
+    """-> {'params': (normalizer, policy_flat), and when present 'value', 'optimizer', 'env_steps', 'policy_counter', 'reset_step',
+    'start_priority' ({'cdf', 'ended', 'failed'}: int32)}."""
     z = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
     t = lambda a: torch.from_numpy(np.asarray(a)).to(device) if device is not None else torch.from_numpy(np.asarray(a))  # noqa: E731
     norm = running_statistics.RunningStatisticsState(*(t(z[f"normalizer/{k}"]) for k in _NORM))
@@ -202,4 +209,6 @@ def load_params(path: str, ppo_network, device=None) -> Dict[str, Any]:
         out["policy_counter"] = t(z["meta/policy_counter"])
     if "meta/reset_step" in z.files:
         out["reset_step"] = t(z["meta/reset_step"])
+    if "meta/start_priority_cdf" in z.files:
+        out["start_priority"] = {k: t(z[f"meta/start_priority_{k}"]) for k in ("cdf", "ended", "failed")}
     return out

@@ -103,3 +103,39 @@ def reset_draws(seed: int, step: IntLike, env: torch.Tensor, nq: int, start_hi: 
     a = (2.0 * math.pi) * u[..., 1::2]
     nz = torch.stack((r * torch.cos(a), r * torch.sin(a)), dim=-1).reshape(env.shape[0], -1)[:, :nq]
     return below(x[:, 0], int(start_hi)), below(x[:, 1], int(num_clips)), (nz * float(noise_scale)).to(torch.float32)
+
+
+def words_u32(t) -> torch.Tensor:
+    """The 32-bit words of an int32 tensor (or of an integer array of values below 2^32) as unsigned values: int64, CPU."""
+    return torch.as_tensor(t).detach().cpu().to(torch.int64) & MASK
+
+
+def weighted_cells(seed: int, step: IntLike, env: torch.Tensor, cdf: torch.Tensor) -> torch.Tensor:
+    """The cells (int64 [B], cell = clip * start_hi + start_frame) that a prioritised fresh reset
+    (vnl_env_reset_done_weighted) draws for the envs with GLOBAL indices `env` at `step` from the table `cdf` (int32 words
+    or unsigned values, [ncell]): #{ c < ncell - 1 : cdf[c] <= x0 } on word x0 of block RESET_INT_BLOCK, the word of
+    reset_draws' start frame.  The last entry is not read."""
+    x0 = _words(seed, step, env, 1, STREAM_RESET, block0=RESET_INT_BLOCK)[:, 0, 0].cpu().contiguous()
+    return torch.searchsorted(words_u32(cdf)[:-1].contiguous(), x0, right=True)
+
+
+def start_priority_table(ended, failed, prior: int = 1, floor_q16: int = 6554,
+                         decay_shift: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """vnl_start_priority_update restated (include/vnl.h): (cdf, ended', failed') as unsigned values, int64 [ncell], from
+    counters given as int32 words or unsigned values.  uint64 throughout: (f + a) << 16 < 2^49, P_c << 32 < 2^64 because
+    P_c <= S < 2^32 for ncell <= 32768."""
+    import numpy as np
+
+    n0, f0 = words_u32(ended).numpy().astype(np.uint64), words_u32(failed).numpy().astype(np.uint64)
+    ncell, a = n0.shape[0], int(prior)
+    assert 1 <= ncell <= 32768 and 1 <= a < (1 << 32) and 1 <= int(floor_q16) <= 65536 and 0 <= int(decay_shift) <= 31
+    n = np.minimum(n0, np.uint64(1 << 20))
+    f = np.minimum(f0, n)
+    s = ((f + np.uint64(a)) << np.uint64(16)) // (n + np.uint64(2 * a))
+    assert int(s.max()) <= 65535
+    p = np.cumsum(s + np.uint64(floor_q16), dtype=np.uint64)
+    assert int(p[-1]) < (1 << 32)
+    cdf = (p << np.uint64(32)) // p[-1]
+    cdf[-1] = 0xFFFFFFFF
+    back = lambda x: torch.from_numpy(x.astype(np.int64))  # noqa: E731
+    return back(cdf), back(n0 >> np.uint64(decay_shift)), back(f0 >> np.uint64(decay_shift))

@@ -146,6 +146,7 @@ def train(
     update_backend: str = "auto",
     policy_noise: str = "generator",
     auto_reset: str = "first_state",
+    start_priority: Any = False,
 ):
     """PPO training (train.py:62-491).
 
@@ -181,6 +182,14 @@ def train(
     evaluator's env keeps "first_state" (EvalWrapper scores each env's first episode only).  The counter of the draws is
     `TrainingState.reset_step` (checkpoint.save_params(reset_step=...) / `restore_from` carry it, like `policy_counter`).
 
+    `start_priority`: False, True or dict(prior=, floor_q16=, decay_shift=); needs auto_reset="fresh".  The fresh resets
+    draw start frame and clip from a table that favours the (clip, start frame) cells whose episodes end before their
+    sub-clip does (envs/start_priority.py StartPriority): the reset kernel counts the outcomes, and once per training step,
+    after the unroll, `update()` turns the counters into the next table -- all on the device.  With several ranks each
+    counts into deltas of its own that `fold_counters` all-reduces into accumulators identical on every rank, so every rank
+    draws from the same table.  `train.last_start_priority` is the object (checkpoint.save_params(start_priority=
+    its state_dict()) / `restore_from` carry table and counters).  The evaluator's env is not prioritised.
+
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
     ~500 launches of microsecond kernels and purely launch-bound.
@@ -205,10 +214,18 @@ def train(
     g_dev = torch.Generator(device=device).manual_seed(seed * 7919 + 101 + rank) if device.type == "cuda" else g_env
     g_eval = torch.Generator(device="cpu").manual_seed(seed * 31 + 7)
 
+    prio = None
+    if start_priority:
+        if auto_reset != "fresh":
+            raise ValueError("start_priority needs auto_reset='fresh'")
+        from ..envs.start_priority import StartPriority
+
+        prio = StartPriority(environment, per_rank_deltas=world > 1,
+                             **(dict(start_priority) if isinstance(start_priority, dict) else {}))
     env = env_wrappers.wrap(environment, episode_length=episode_length, action_repeat=action_repeat,
                             randomization_fn=bind_randomization(randomization_fn, local_envs, seed),
                             reset_info_on_autoreset=reset_info_on_autoreset, auto_reset=auto_reset,
-                            auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs)
+                            auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs, start_priority=prio)
     env_state = env.reset(g_env)
 
     normalize = (lambda x, y: x)
@@ -256,6 +273,8 @@ def train(
             training_state.policy_counter.copy_(ck["policy_counter"])
         if training_state.reset_step is not None and "reset_step" in ck:  # (the episode draws go on, not from step 0 again)
             training_state.reset_step.copy_(ck["reset_step"])
+        if prio is not None and "start_priority" in ck:
+            prio.load_state_dict(ck["start_priority"])
 
     from .intention_policy_network import LeafParams
 
@@ -520,6 +539,9 @@ def train(
         """train.py:293-349."""
         nonlocal env_state
         chunks = unroll_chunks(batch_size * num_minibatches // num_envs)
+        if prio is not None:  # (outside the captured unroll: the outcomes just counted shape the next unroll's draws)
+            prio.fold()
+            prio.update()
         # [U, T, B, ...] -> swapaxes(1,2) -> reshape(-1, T, ...)   (train.py:323-327)
         data = chunks[0].map(lambda x: x) if len(chunks) == 1 else None
         if data is None:
@@ -633,4 +655,5 @@ def train(
     train.last_training_state = training_state  # value net / optimiser for checkpoint-resume (beyond the reference)
     train.last_ppo_network = ppo_network
     train.last_env_state = env_state  # the training envs as the run leaves them
+    train.last_start_priority = prio  # the StartPriority of the run (None without start_priority)
     return make_policy, params, metrics
