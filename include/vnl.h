@@ -181,7 +181,8 @@ int vnl_env_reset(vnl_env*, const int32_t* start_frame, const float* noise, cons
  * vnl_env_reset given the recorded start_frame, clip_id and noise returns the same bits.
  * Written for a reset env: the pipeline state (qpos .. qfrc_actuator), obs, traj, termination_error, cur_frame,
  * sub_clip_frame (0) and clip_id.  NOT written: reward, done and metrics, which keep the terminal step's values as under
- * brax's auto-reset.  Nothing of an env whose mask is 0 is touched; per-env domain tables stay as they are.
+ * brax's auto-reset.  Nothing of an env whose mask is 0 is touched; per-env domain tables stay as they are unless ranges are set
+ * (vnl_env_set_domain_ranges below: then the domain of every reset env is drawn anew first).
  * Then, for EVERY env, each of the `num_logs` (0..8) log descriptors copies row src[e][width] to log[e][width] (32-bit
  * words, as vnl_rollout_post moves rows): next_observation and the logged info fields of a rollout record the post-reset
  * values without a launch of their own.
@@ -255,7 +256,7 @@ int vnl_env_step(vnl_env*, const float* action, const vnl_state* state, void* st
 int vnl_env_fk(vnl_env* env, const float* qpos, const vnl_state* state, void* stream);
 
 /* Domain randomisation (brax `randomization_fn`, MJX semantics): per-env values of four raw model fields, fixed until the
- * next call (auto-reset leaves them as they are).  Device pointers, float64, row-major [num_envs][n]; a null field pointer
+ * next call (auto-reset leaves them as they are, unless vnl_env_set_domain_ranges has set ranges).  Device pointers, float64, row-major [num_envs][n]; a null field pointer
  * means the model's value for every env:
  *   cg_friction  [ncg]  sliding friction of each collidable geom's contact rows (column 0 of the compiled cg_friction)
  *   act_gain     [nu]   gainprm[0]
@@ -264,12 +265,52 @@ int vnl_env_fk(vnl_env* env, const float* qpos, const vnl_state* state, void* st
  * derived per env by the upload's float64 expression, so a domain equal to the compiled values gives bit-identical tables.
  * Every value must be finite, friction > 0, damping and armature >= 0 (else VNL_ERR_ARG).  The call waits for `stream`,
  * copies and derives into library-owned tables; reset / step then run the randomised kernels.  A null `vnl_domain*` clears
- * the domain.  vnl_env_scratch reads the tables back: "dom_mu", "dom_invw" [num_envs][ncg], "dom_gain" [num_envs][nu],
+ * the domain (and the ranges of vnl_env_set_domain_ranges).  vnl_env_scratch reads the tables back: "dom_mu", "dom_invw" [num_envs][ncg], "dom_gain" [num_envs][nu],
  * "dom_damp", "dom_arm" [num_envs][nv] (row stride = the returned count, vreal elements; no debug mode needed). */
 typedef struct vnl_domain {
   const double *cg_friction, *act_gain, *dof_damping, *dof_armature;
 } vnl_domain;
 int vnl_env_set_domain(vnl_env* env, const vnl_domain* domain, void* stream);
+
+/* A new domain per EPISODE (opt-in): per-element bounds of the four fields of vnl_domain, stored with the env.  With ranges
+ * set, vnl_env_reset_done / vnl_env_reset_done_weighted draw the domain of every env they reset anew, inside the reset
+ * kernel: after the start-priority counting (which reads the finished episode), before the noise and integer draws and the
+ * reset body -- the forward pass of the reset, and qacc_warmstart with it, belong to the new domain.  Without ranges every
+ * path is what it is without this entry, bit for bit.
+ * The draw, from a third block range of stream 3 of vnl_reset_noise (beside the noise blocks 0.. and the integer block
+ * 0x80000000), for field f (0 cg_friction, 1 act_gain, 2 dof_damping, 3 dof_armature) and element j:
+ *   counter = (0x40000000 + initial * 0x20000000 + f * 0x00100000 + j / 4, env_offset + e, step low 32 bits,
+ *              (step >> 32) << 2 | 3), word j % 4 of the block; a SHARED field (bit f of `shared`): word 0 of block j / 4 = 0 for
+ *              every element -- one uniform per (env, episode) for the whole field
+ *   u = (x + 0.5) * 2^-32                 float64, exact, strictly inside (0, 1)
+ *   v = lo[j] + u * (hi[j] - lo[j])       float64; the difference, the product and the sum each rounded on its own (no fused
+ *                                         multiply-add), so lo == hi gives exactly lo
+ *   tables: dom_gain / dom_damp / dom_arm / dom_mu = (real)v; dom_invw = (real) of the upload's float64 expression
+ *           (t + v^2 t) 2 v^2 / impratio, t = cg_t[j] -- the bits vnl_env_set_domain produces from the same float64 values.
+ * An env's draw depends on (seed, step, env_offset + e, initial) alone.  ppo_imitation/philox.py (domain_draws) restates it.
+ * vnl_env_set_domain_ranges follows the contract of vnl_env_set_domain: it waits for `stream`, copies the bounds (and cg_t,
+ * impratio: what the derivation needs, as float64) into library-owned device memory, and validates on the host first --
+ * VNL_ERR_ARG with the field's name, nothing launched and nothing changed, unless every value is finite, lo <= hi, friction
+ * lo > 0, damping and armature lo >= 0, and lo[f] / hi[f] are both given or both null.  An env without a four-field domain
+ * gets its tables at the compiled values and runs the randomised kernels from then on; an env with vnl_env_set_domain
+ * values keeps them until its first redraw.  A later vnl_env_set_domain overwrites the tables, not the ranges;
+ * vnl_env_set_domain(null) also clears the ranges.  The body tables (vnl_env_set_body_domain) are never redrawn.
+ * vnl_env_redraw_domain is the same device function as a launch of its own -- the domain of the FIRST episode
+ * (initial = 1: a block range of its own, so that it differs from a reset at the same counter) and the tests' handle on the
+ * draw: seed, step_base, step_offset and env_offset of the descriptor are read; a null mask = every env.  VNL_ERR_ARG
+ * without ranges, for a null descriptor / step_base, a negative offset, or initial outside 0..1. */
+typedef struct vnl_domain_ranges {
+  /* fields in the order of vnl_domain: cg_friction [ncg], act_gain [nu], dof_damping [nv], dof_armature [nv].
+     DEVICE float64 [n_f] each: ABSOLUTE bounds per element.  lo[f] and hi[f] both null: field f is never redrawn. */
+  const double* lo[4];
+  const double* hi[4];
+  uint32_t shared; /* bit f set: ONE uniform per (env, episode) for the whole field f; clear: one per element */
+  uint32_t pad_;
+} vnl_domain_ranges;
+int vnl_env_set_domain_ranges(vnl_env*, const vnl_domain_ranges*, void* stream); /* null descriptor clears */
+int vnl_env_redraw_domain(vnl_env*, const float* mask /* [num_envs] or null = every env */,
+                          const vnl_reset_noise* /* seed, step_base, step_offset, env_offset are read */,
+                          int32_t initial, void* stream);
 
 /* Domain randomisation of the inertial fields: per-env body mass, principal moments and centre of mass over the bodies of
  * the model AS GIVEN (nbody of vnl_dims: welded bodies included), float64 DEVICE pointers, row-major

@@ -19,6 +19,12 @@ workgroups from the reset envs' forward pass.
 drawn from a table by a wave-wide search, the ended episodes counted by atomics; `update()` after every replay, as train()
 runs it after every unroll), alternated in this one process; and the update kernel alone at 15,040 cells (64 clips x 235
 frames; median of 20 launches between event pairs).
+
+--domain-ranges: the legs are fresh mode on an identity-domain env (with_domain of the compiled values: the randomised
+kernels, the tables never written) without and with ranges on all four fields (with_domain_ranges: every reset env draws its
+friction, gain, damping and armature anew inside the reset launch), alternated in this one process; with --per-step the
+reset launch of every step and the launch alone at fixed shares, for both.  --mode fresh_domain is the first of these legs on
+its own (no new entry point is called: it also runs against an older library, for the comparison of the default paths).
 """
 from __future__ import annotations
 
@@ -44,6 +50,9 @@ def resource_lines() -> dict:
             if "vnl_priority_kernel" in name:
                 kv = dict(re.findall(r"(\S[^=]*?)=(-?\d+)(?=\s|$)", rest))
                 out["vnl_priority_kernel"] = {k: int(v) for k, v in kv.items() if k in keep}
+            if "vnl_redraw_domain_kernel" in name:
+                kv = dict(re.findall(r"(\S[^=]*?)=(-?\d+)(?=\s|$)", rest))
+                out["redraw_" + re.sub(r"^_Z\d+vnl_redraw_domain_kernelI|EvPK.*$", "", name)] = {k: int(v) for k, v in kv.items() if k in keep}
             if "vnl_reset_done_kernel" in name:
                 kv = dict(re.findall(r"(\S[^=]*?)=(-?\d+)(?=\s|$)", rest))
                 out[re.sub(r"^_Z\d+vnl_reset_done_kernelI|EvPK.*$", "", name)] = {k: int(v) for k, v in kv.items() if k in keep}
@@ -57,9 +66,10 @@ def main() -> None:
     ap.add_argument("--replays", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--mode", choices=("both", "first_state", "fresh"), default="both")
+    ap.add_argument("--mode", choices=("both", "first_state", "fresh", "fresh_domain"), default="both")
     ap.add_argument("--per-step", action="store_true", help="also time every control step of one eager fused unroll in fresh mode")
     ap.add_argument("--start-priority", action="store_true", help="legs: fresh mode without and with a StartPriority")
+    ap.add_argument("--domain-ranges", action="store_true", help="legs: fresh mode on an identity-domain env without and with ranges")
     args = ap.parse_args()
 
     import numpy as np
@@ -75,10 +85,21 @@ def main() -> None:
     modes = ("first_state", "fresh") if args.mode == "both" else (args.mode,)
     if args.start_priority:
         modes = ("fresh", "fresh_priority")
+    if args.domain_ranges:
+        modes = ("fresh_domain", "fresh_ranges")
     priorities = {}
 
     def setup(mode):
         base = RodentTracking(H.reference_clip(), num_envs=B, device=dev, **H.env_kwargs())
+        if mode in ("fresh_domain", "fresh_ranges"):
+            import domain_cases as D
+
+            base = base.with_domain(D.identity(base.sys, B))
+            if mode == "fresh_ranges":
+                from vnl_brax_imitation_amd.envs.rodent import domain_ranges_scaled
+
+                base = base.with_domain_ranges(domain_ranges_scaled(base.sys, friction=(0.5, 1.5), gain=(0.7, 1.3),
+                                                                    damping=(0.5, 2.0), armature=(0.5, 2.0)))
         ep = EpisodeWrapper(base, episode_length=150, action_repeat=1)
         # (the default mode is constructed as before the keyword existed: this file also runs against an older library)
         if mode == "fresh_priority":
@@ -158,12 +179,15 @@ def main() -> None:
             torch.cuda.synchronize(dev)
             us.append(e0.elapsed_time(e1) * 1e3)
         out["update_kernel_us_at_15040_cells"] = round(float(np.median(us[3:])), 1)
+    elif args.domain_ranges:
+        out["ranges_minus_domain_ms"] = round(med["fresh_ranges"] - med["fresh_domain"], 5)
     elif len(modes) == 2:
         out["fresh_minus_first_state_ms"] = round(med["fresh"] - med["first_state"], 5)
-    if args.per_step and "fresh" in modes:
+    for leg in [m for m in modes if m != "first_state" and m != "fresh_priority"] if args.per_step else ():
         # where the time goes: one eager fused unroll, an event pair around the reset launch of every step -- steps on which
         # (nearly) nobody resets show the launch of empty workgroups, the others the reset envs' forward pass
-        env, policy, state = setup("fresh")
+        env, policy, state = setup(leg)
+        tag = "" if leg == "fresh" else "_" + leg
         base = env.unwrapped
         real = base.reset_done
         spans = []
@@ -184,7 +208,7 @@ def main() -> None:
             rows = [(round(a.elapsed_time(b) * 1e3, 1), round(float((1 - data.discount[t]).mean()), 4))
                     for t, (a, b) in enumerate(spans)]
         base.reset_done = real
-        out["reset_launch_us_and_share_by_step"] = rows
+        out["reset_launch_us_and_share_by_step" + tag] = rows
         # .. and the launch alone at fixed shares (median of 20 launches, the two logs of the unroll): share 0 is the cost of
         # 4096 workgroups that read a mask word and copy two rows
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -201,7 +225,7 @@ def main() -> None:
                 torch.cuda.synchronize(dev)
                 us.append(e0.elapsed_time(e1) * 1e3)
             alone[f"{share:.4f}"] = round(float(np.median(us[3:])), 1)
-        out["reset_launch_alone_us_by_share"] = alone
+        out["reset_launch_alone_us_by_share" + tag] = alone
     out["resources"] = resource_lines()
     print(json.dumps(out))
 

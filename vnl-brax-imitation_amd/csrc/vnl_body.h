@@ -3056,7 +3056,7 @@ struct EnvWaveT {
   // limit, not the env's doing) and anything out of range count nothing.
   // The draw: word x0 of the block the uniform draws use, cell = #{ c < ncell - 1 : cdf[c] <= x0 } (vnl_cdf_cell).  Every
   // lane computes the block -- ten rounds of integer multiplies, cheaper than a broadcast through memory.
-  VNL_HD void reset_fresh_weighted(const ResetDoneArgs& a, uint32_t c1, uint32_t c2, uint32_t c3) const {
+  VNL_HD void prio_count(const ResetDoneArgs& a) const {
     const int hi = (int)a.start_hi;
     VNL_SERIAL {
       if (a.prio.ended) {
@@ -3070,6 +3070,11 @@ struct EnvWaveT {
         }
       }
     }
+  }
+  // (`counted`: the counting was done already -- reset_fresh of an env with domain ranges counts before it redraws)
+  VNL_HD void reset_fresh_weighted(const ResetDoneArgs& a, uint32_t c1, uint32_t c2, uint32_t c3, bool counted) const {
+    const int hi = (int)a.start_hi;
+    if (!counted) prio_count(a);
     uint32_t x[4];
     philox4x32_10(0x80000000u, c1, c2, c3, a.key0, a.key1, x);
     const int cell = vnl_cdf_cell(a.prio.cdf, a.prio.ncell, x[0], lane);
@@ -3080,10 +3085,51 @@ struct EnvWaveT {
     }
   }
 
+  // The physical domain of THIS env drawn anew (include/vnl.h: vnl_domain_ranges; randomised instantiations only): the four
+  // raw fields uniform between their per-element bounds, from a third block range of stream 3 --
+  //   counter = (0x40000000 + initial * 0x20000000 + f * 0x00100000 + j / 4, c1, c2, c3), element j of field f = word j % 4
+  // (a SHARED field: every element takes word 0 of block 0) -- u = (x + 0.5) 2^-32 and v = lo + u * (hi - lo) in float64, each
+  // operation rounded on its own (vnl_domain_value), then the tables as vnl_env_set_domain derives them from v: (vreal)v and,
+  // for friction, the inverse weight by the upload's expression.  Every lane computes the block of its element: ten rounds
+  // of integer multiplies against a broadcast.  Lanes store elements lane, lane + 64, .. through the WRITABLE views of
+  // KernelConsts::rng; par<F>() reads them from other lanes, so a VNL_SYNC_GLOBAL() must follow before the first read.
+  VNL_HD void redraw_domain(uint32_t key0, uint32_t key1, uint32_t c1, uint32_t c2, uint32_t c3, int initial) const {
+    if constexpr (SP::dom) {
+      const VNL_CAS DevDomainRanges& r = kc->rng;
+      const int n[4] = {MI(ncg), MI(nu), MI(nv), MI(nv)};
+      vreal* const out[4] = {r.cg_mu, r.act_gain, r.dof_damping, r.dof_armature};
+      const double impratio = r.cg_t[MI(ncg)];
+      for (int f = 0; f < 4; f++) {
+        const double *lo = r.lo[f], *hi = r.hi[f];
+        if (!lo) continue;
+        const bool one = (r.shared >> f) & 1u;
+        const uint32_t b0 = 0x40000000u + (initial ? 0x20000000u : 0u) + (uint32_t)f * 0x00100000u;
+        VNL_FOR(j, n[f]) {
+          uint32_t x[4];
+          philox4x32_10(one ? b0 : b0 + (uint32_t)(j >> 2), c1, c2, c3, key0, key1, x);
+          const int q = one ? 0 : (j & 3);
+          const uint32_t w = q == 0 ? x[0] : (q == 1 ? x[1] : (q == 2 ? x[2] : x[3]));
+          const double v = vnl_domain_value(lo[j], hi[j], w);
+          out[f][(size_t)e * n[f] + j] = (vreal)v;
+          if (f == 0) r.cg_invweight[(size_t)e * n[0] + j] = (vreal)contact_invweight(r.cg_t[j], v, impratio);
+        }
+      }
+    }
+  }
+
+  // Order: the start-priority counting (it reads the finished episode), the domain redraw, the noise and integer draws, the
+  // reset body -- whose forward pass, and the warm start it leaves, belong to the new domain.
   VNL_HD void reset_fresh(const ResetDoneArgs& a, int* trace_base) const {
     const int nq = MI(nq), nblk = (nq + 3) >> 2;
     const int64_t step = *a.step_base + a.step_offset;
     const uint32_t c1 = a.env0 + (uint32_t)e, c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
+    bool counted = false;
+    if constexpr (SP::dom) {
+      if (kc->rng.on) {
+        if (a.prio.cdf) prio_count(a), counted = true;
+        redraw_domain(a.key0, a.key1, c1, c2, c3, 0);  // (the join below, before reset_core, stands between these stores and par<F>())
+      }
+    }
     vreal* nz = a.noise + (size_t)e * nq;
     VNL_FOR(b, nblk) {
       uint32_t x[4];
@@ -3095,7 +3141,7 @@ struct EnvWaveT {
         if (4 * b + q < nq) nz[4 * b + q] = vreal(v[q] * a.noise_scale);
     }
     if (a.prio.cdf) {
-      reset_fresh_weighted(a, c1, c2, c3);
+      reset_fresh_weighted(a, c1, c2, c3, counted);
     } else {
       VNL_SERIAL {
         uint32_t x[4];
@@ -3105,7 +3151,7 @@ struct EnvWaveT {
         a.clip_id[e] = clip, st.clip_id[e] = clip;
       }
     }
-    VNL_SYNC_GLOBAL();  // (every lane reads the start frame and clip that lane 0 stored, and the noise row)
+    VNL_SYNC_GLOBAL();  // (every lane reads the start frame and clip that lane 0 stored, the noise row, and the redrawn tables)
     reset_core<true>(a.start_frame, a.noise, trace_base);
   }
 

@@ -44,3 +44,14 @@ int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, 
                        dump, trace);
   return (int)hipGetLastError();
 }
+
+int vnl_domain_redraw_(const KernelConsts* kc, int spec, int B, void* stream, const float* mask, const int64_t* step_base,
+                       int64_t step_offset, uint32_t key0, uint32_t key1, uint32_t env0, int initial) {
+  if (spec)
+    hipLaunchKernelGGL((vnl_redraw_domain_kernel<VnlSpecDom<VnlSpecRodent>>), dim3(B), dim3(64), 0, (hipStream_t)stream, kc, mask,
+                       step_base, step_offset, key0, key1, env0, initial);
+  else
+    hipLaunchKernelGGL((vnl_redraw_domain_kernel<VnlSpecDom<VnlSpecGeneric>>), dim3(B), dim3(64), 0, (hipStream_t)stream, kc, mask,
+                       step_base, step_offset, key0, key1, env0, initial);
+  return (int)hipGetLastError();
+}

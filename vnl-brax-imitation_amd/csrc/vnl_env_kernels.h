@@ -142,3 +142,19 @@ __global__ void VNL_ENV_KERNEL vnl_reset_done_kernel(const KernelConsts* kc, Dev
     VNL_FOR(i, a.logs[q].width) log[i] = src[i];
   }
 }
+
+// The domain redraw of EnvWaveT::reset_fresh as a launch of its own (vnl_env_redraw_domain: the first episode's domain, and
+// what the tests compare the fused redraw with): the envs whose mask is set, or every env with a null mask.  Randomised
+// instantiations only; no LDS, no state.
+template <class SP>
+__global__ void __launch_bounds__(64) vnl_redraw_domain_kernel(const KernelConsts* kc, const float* mask, const int64_t* step_base,
+                                                               int64_t step_offset, uint32_t key0, uint32_t key1, uint32_t env0,
+                                                               int initial) {
+  const unsigned e = blockIdx.x, lane = threadIdx.x;
+  if (mask && mask[e] == 0.f) return;
+  const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
+  const DevState none{};
+  EnvWaveT<SP> w{k->m, k->ev, none, k->L, nullptr, e, lane, k, nullptr};
+  const int64_t step = *step_base + step_offset;
+  w.redraw_domain(key0, key1, env0 + e, (uint32_t)step, ((uint32_t)(step >> 32) << 2) | 3u, initial);
+}

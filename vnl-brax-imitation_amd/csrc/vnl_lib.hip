@@ -121,6 +121,9 @@ struct vnl_env {
   vreal* dom = nullptr;  // the four-field tables, then the body tables [B][nd | 3 nd | 6 nd | 1] (nd dynamic bodies)
   int has_dom = 0;  // 1: vnl_env_reset / vnl_env_step launch the randomised instantiations (csrc/vnl_domain.hip)
   int has_dom4 = 0, has_body = 0;  // which part was set (vnl_env_set_domain / vnl_env_set_body_domain); the other reads as compiled
+  // vnl_env_set_domain_ranges: the device copy of the bounds ([ncg] cg_t | impratio | lo, hi of every field given), float64
+  double* rng_buf = nullptr;
+  int has_ranges = 0;
   // vnl_env_set_body_domain: the inertial fields of the model AS GIVEN and the fold of its welded bodies, kept from the upload
   struct FuseMap* fmap = nullptr;
   std::vector<double> mass0, ipos0, ifull0, inertia0, iquat0;  // (inertia0 / iquat0 empty: the blob does not carry them)
@@ -347,7 +350,7 @@ static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm)
 }
 
 // inverse weight of a contact's rows (constraint._instantiate_contact): at upload and, per env, in vnl_env_set_domain
-static double contact_invweight(double t, double mu, double impratio) { return (t + mu * mu * t) * 2 * mu * mu / impratio; }
+// (contact_invweight: vnl_types.h -- shared with the device redraw of the domain)
 
 static VnlDims dims_of(const DevModel& d) {
   return VnlDims{d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ncg, d.ncon, d.nlimit, d.nefc, d.nM, d.iterations, d.ls_iterations, d.eulerdamp,
@@ -1078,6 +1081,8 @@ int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* 
                      vreal* dump, vreal* dump_mid, int* trace, const vnl_post_desc& post);
 int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds,
                            const ResetDoneArgs& a, vreal* dump, int* trace);
+int vnl_domain_redraw_(const KernelConsts* kc, int spec, int B, void* stream, const float* mask, const int64_t* step_base,
+                       int64_t step_offset, uint32_t key0, uint32_t key1, uint32_t env0, int initial);
 
 static int to_dev_state(const vnl_state* s, DevState* d) {
   const void* ptrs[] = {s->qpos, s->qvel, s->act, s->qacc_warmstart, s->xpos, s->xquat, s->subtree_com1,
@@ -1366,6 +1371,15 @@ static int domain_tables(vnl_env* env) {
   return VNL_OK;
 }
 
+static int clear_domain_ranges(vnl_env* env) {
+  if (env->has_ranges) {
+    const DevDomainRanges none{};
+    HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, rng), &none, sizeof(DevDomainRanges), hipMemcpyHostToDevice));
+  }
+  env->has_ranges = 0;
+  return VNL_OK;
+}
+
 extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* stream) {
   if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_domain: null env");
   DeviceGuard guard(env->device);
@@ -1383,7 +1397,7 @@ extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* str
       if (!tab.empty()) HIPCHK(hipMemcpy(env->dom, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
     }
     env->has_dom4 = 0, env->has_dom = env->has_body;
-    return VNL_OK;
+    return clear_domain_ranges(env);  // (ranges without a four-field domain would redraw tables nobody owns)
   }
   struct Field {
     const char* name;
@@ -1420,6 +1434,92 @@ extern "C" int vnl_env_set_domain(vnl_env* env, const vnl_domain* dom, void* str
   if (rc != VNL_OK) return rc;
   if (!tab.empty()) HIPCHK(hipMemcpy(env->dom, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
   env->has_dom4 = 1, env->has_dom = 1;
+  return VNL_OK;
+}
+
+// Ranges of the domain redraw at fresh resets (include/vnl.h: vnl_domain_ranges).  The contract of vnl_env_set_domain: waits
+// for `stream`, reads the bounds to the host, validates, and only then allocates and writes.
+extern "C" int vnl_env_set_domain_ranges(vnl_env* env, const vnl_domain_ranges* rg, void* stream) {
+  if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_domain_ranges: null env");
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+#ifndef VNL_FORKJOIN_DEFINED
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+#else
+  (void)stream;
+#endif
+  if (!rg) return clear_domain_ranges(env);
+  const DevModel& d = env->dm;
+  const struct {
+    const char* name;
+    int n;
+    int rule;  // 0: lo > 0, 1: lo >= 0, 2: finite only
+  } fields[4] = {{"cg_friction", d.ncg, 0}, {"act_gain", d.nu, 2}, {"dof_damping", d.nv, 1}, {"dof_armature", d.nv, 1}};
+  if (rg->shared & ~0xFu) return fail(VNL_ERR_ARG, "vnl_env_set_domain_ranges: shared has bits beyond the four fields");
+  std::vector<double> buf(env->cg_t.begin(), env->cg_t.end());
+  buf.resize((size_t)d.ncg, 0.0);
+  buf.push_back(env->impratio);
+  size_t at[4] = {0, 0, 0, 0};  // offset of lo[f] in buf (hi[f] follows it), 0: the field has no bounds
+  for (int f = 0; f < 4; f++) {
+    const auto& F = fields[f];
+    if (!rg->lo[f] != !rg->hi[f])
+      return fail(VNL_ERR_ARG, "vnl_env_set_domain_ranges: %s: lo and hi must both be given or both be null", F.name);
+    if (!rg->lo[f]) continue;
+    at[f] = buf.size();
+    buf.resize(buf.size() + 2 * (size_t)F.n);
+    double *lo = buf.data() + at[f], *hi = lo + F.n;
+    if (F.n > 0) {
+      HIPCHK(hipMemcpy(lo, rg->lo[f], F.n * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hi, rg->hi[f], F.n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < F.n; k++) {
+      const bool ok = std::isfinite(lo[k]) && std::isfinite(hi[k]) && lo[k] <= hi[k] &&
+                      (F.rule == 2 || (F.rule == 1 ? lo[k] >= 0 : lo[k] > 0));
+      if (!ok) {
+        char where[96];
+        snprintf(where, sizeof(where), "index %d (lo %g, hi %g)", k, lo[k], hi[k]);
+        return fail(VNL_ERR_ARG, F.rule == 0   ? "vnl_env_set_domain_ranges: %s needs finite 0 < lo <= hi: %s"
+                                 : F.rule == 1 ? "vnl_env_set_domain_ranges: %s needs finite 0 <= lo <= hi: %s"
+                                               : "vnl_env_set_domain_ranges: %s needs finite lo <= hi: %s",
+                    F.name, where);
+      }
+    }
+  }
+  int rc = domain_tables(env);  // (an env without a domain: the tables at the compiled values)
+  if (rc != VNL_OK) return rc;
+  if (!env->rng_buf) {  // room for every field, whatever this call gives
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, ((size_t)d.ncg + 1 + 2 * ((size_t)d.ncg + d.nu + 2 * (size_t)d.nv)) * sizeof(double)));
+    env->allocs.push_back(p);
+    env->rng_buf = (double*)p;
+  }
+  HIPCHK(hipMemcpy(env->rng_buf, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+  const size_t B = (size_t)env->B;
+  DevDomainRanges dr{};
+  dr.on = 1, dr.shared = rg->shared, dr.cg_t = env->rng_buf;
+  for (int f = 0; f < 4; f++)
+    if (at[f]) dr.lo[f] = env->rng_buf + at[f], dr.hi[f] = env->rng_buf + at[f] + fields[f].n;
+  dr.cg_mu = env->dom, dr.cg_invweight = env->dom + B * d.ncg, dr.act_gain = env->dom + 2 * B * d.ncg;  // (the layout of domain_tables)
+  dr.dof_damping = dr.act_gain + B * d.nu, dr.dof_armature = dr.dof_damping + B * d.nv;
+  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, rng), &dr, sizeof(DevDomainRanges), hipMemcpyHostToDevice));
+  env->has_ranges = 1, env->has_dom4 = 1, env->has_dom = 1;
+  return VNL_OK;
+}
+
+// The redraw of vnl_env_reset_done as a launch of its own (EnvWaveT::redraw_domain; include/vnl.h)
+extern "C" int vnl_env_redraw_domain(vnl_env* env, const float* mask, const vnl_reset_noise* noise, int32_t initial, void* stream) {
+  if (!env || !noise) return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: null argument");
+  if (!env->has_ranges) return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: the env has no ranges (vnl_env_set_domain_ranges)");
+  if (!noise->step_base) return fail(VNL_ERR_ARG, "vnl_reset_noise: step_base is null (a device pointer to the step counter)");
+  if (noise->step_offset < 0 || noise->env_offset < 0)
+    return fail(VNL_ERR_ARG, "vnl_reset_noise: step_offset and env_offset must not be negative");
+  if (noise->env_offset >= 0xFFFFFFFFll - (int64_t)env->B)
+    return fail(VNL_ERR_ARG, "vnl_reset_noise: env_offset + num_envs must stay below 2^32 - 1");
+  if (initial != 0 && initial != 1) return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: initial must be 0 or 1");
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+  HIPCHK((hipError_t)vnl_domain_redraw_(env->kc, env->spec, env->B, stream, mask, noise->step_base, noise->step_offset,
+                                        (uint32_t)noise->seed, (uint32_t)(noise->seed >> 32), (uint32_t)noise->env_offset, initial));
   return VNL_OK;
 }
 

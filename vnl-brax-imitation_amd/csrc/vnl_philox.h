@@ -30,6 +30,20 @@ VNL_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, ui
   x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
 }
 
+// A value uniform between two bounds from one word (the domain redraw, EnvWaveT::redraw_domain): u = (x + 0.5) 2^-32, exact in
+// float64 and strictly inside (0, 1), then lo + u * (hi - lo) with the difference, the product and the sum each rounded on
+// its own -- no multiply-add contraction, so that the device, the host build and philox.py (domain_draws) give the same bits.
+// lo == hi gives lo; lo < hi gives a value in [lo, hi].
+VNL_HD double vnl_domain_value(double lo, double hi, uint32_t x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double u = ((double)x + 0.5) * 0x1p-32;
+  const double w = hi - lo;
+  const double p = u * w;
+  return lo + p;
+}
+
 // One Box-Muller pair from two words: u = ((x >> 8) + 0.5) 2^-24 = (2 k + 1) 2^-25 with k = x >> 8.  float32 holds u exactly
 // for k < 2^23 and 1 - u exactly above, so the upper half goes through ln u = log1p(-(1 - u)) and the angle through
 // cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u)): no rounding of u anywhere (rounded to 1 it would

@@ -187,6 +187,21 @@ struct VnlDims {
 #define VNL_NPROF_SLOTS 0
 #endif
 #endif
+/* The contact rows' inverse weight from friction: t = invweight0 of the world + that of the geom's body.  The one expression
+ * of the upload (float64), of vnl_env_set_domain and of the device redraw: no multiply-add contraction, so that host and
+ * device round alike. */
+#if defined(__HIPCC__)
+#define VNL_HOST_DEVICE __host__ __device__
+#else
+#define VNL_HOST_DEVICE
+#endif
+VNL_HOST_DEVICE inline double contact_invweight(double t, double mu, double impratio) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return (t + mu * mu * t) * 2 * mu * mu / impratio;
+}
+
 constexpr int vnl_imax(int a, int b) { return a > b ? a : b; }
 constexpr int vnl_words(long bytes) { return (int)((bytes + (long)sizeof(vreal) - 1) / (long)sizeof(vreal)); }
 constexpr WsLayout vnl_make_layout(const VnlDims& d) {
@@ -283,6 +298,18 @@ struct DevDomain {
   const vreal *total_mass_inv;                        /* [B] */
 };
 
+/* Ranges of the domain redraw at fresh resets (vnl_env_set_domain_ranges; EnvWaveT::redraw_domain), library-owned device
+ * memory.  Fields in the order of vnl_domain: cg_friction, act_gain, dof_damping, dof_armature. */
+struct DevDomainRanges {
+  int on;          /* 0: no ranges, nothing below is read */
+  uint32_t shared; /* bit f: one uniform per (env, episode) for the whole field f */
+  const double *lo[4], *hi[4]; /* [n_f] absolute bounds per element; both null: field f is never redrawn */
+  const double* cg_t;          /* [ncg] what the contact rows' inverse weight is derived from, then impratio at [ncg] */
+  /* WRITABLE views of the five tables DevDomain points at (the same allocation): the redraw stores through these, the
+     kernels go on reading through DevDomain */
+  vreal *cg_mu, *cg_invweight, *act_gain, *dof_damping, *dof_armature;
+};
+
 /* Everything the env kernels read that does not change between launches, in one device buffer.  The kernels read
  * it through the CONSTANT address space (scalar loads at the point of use) instead of taking ~350 SGPRs' worth of
  * by-value kernel arguments, which the compiler kept alive across the whole kernel by spilling them to VGPR lanes. */
@@ -291,5 +318,6 @@ struct KernelConsts {
   DevEnv ev;
   WsLayout L;
   DevDomain dom; /* (after L: the offsets of m, ev and L that the unrandomised kernels read stay as they are) */
+  DevDomainRanges rng;
 };
 

@@ -61,6 +61,21 @@ def _load_model(mjcf_path: str, scale_factor: float, solver: str, iterations: in
     raise FileNotFoundError(f"{mjcf_path} not found and no packaged compiled model {packaged}")
 
 
+def domain_ranges_scaled(sys, friction=(0.5, 1.5), gain=None, damping=None, armature=None) -> Dict[str, tuple]:
+    """`ranges` for `with_domain_ranges`: absolute (lo, hi) float64 arrays as multiples (lo, hi) of the compiled values of
+    `sys` (a CompiledModel); a field given as None is left out -- it is never redrawn.  A compiled value that is negative
+    (a gain may be) gets its two multiples in ascending order."""
+    compiled = {"cg_friction": np.asarray(sys.cg_friction, np.float64)[:, 0], "act_gain": np.asarray(sys.act_gain, np.float64),
+                "dof_damping": np.asarray(sys.dof_damping, np.float64), "dof_armature": np.asarray(sys.dof_armature, np.float64)}
+    out = {}
+    for k, mult in (("cg_friction", friction), ("act_gain", gain), ("dof_damping", damping), ("dof_armature", armature)):
+        if mult is None:
+            continue
+        a, b = compiled[k] * float(mult[0]), compiled[k] * float(mult[1])
+        out[k] = (np.minimum(a, b), np.maximum(a, b))
+    return out
+
+
 def _clamped_take(x: np.ndarray, idx: Sequence[int], axis: int) -> np.ndarray:
     """x[..., idx, ...] with JAX's clamp-out-of-range gather semantics."""
     idx = np.clip(np.asarray(idx, dtype=np.int64), 0, x.shape[axis] - 1)
@@ -199,13 +214,31 @@ class RodentTracking(Env):
         new = object.__new__(type(self))
         new.__dict__.update(self._config_attrs)
         new._build(self._build_args[0], int(num_envs), *self._build_args[1:])
+        if self._domain_ranges is not None:  # (the ranges, not the tables: the new env's tables hold the compiled values)
+            new._set_domain_ranges(self._domain_ranges)
         return new
 
     _domain = None  # {field: (num_envs, n) float64 tensor} of a randomised env (with_domain), else None
     _body_domain = None  # {field: (num_envs, nbody[, 3]) float64 tensor} of a body-randomised env (with_body_domain), else None
 
-    def _with_domains(self, tables, body_tables) -> "RodentTracking":
-        """A new env of this configuration and num_envs with the given parts of a domain (already validated; None: unset)."""
+    _domain_ranges = None  # ({field: (lo, hi) float64 (n,) CPU tensors}, shared field names) of with_domain_ranges, else None
+
+    def _set_domain_ranges(self, ranges) -> None:
+        """vnl_env_set_domain_ranges of already validated ranges (the library copies them: synchronous)"""
+        bounds, shared = ranges
+        desc, keep = _lib.DomainRanges(), []
+        for f, k in enumerate(DOMAIN_FIELDS):
+            if k in bounds:
+                lo, hi = (t.to(self.device).contiguous() for t in bounds[k])
+                keep += [lo, hi]
+                desc.lo[f], desc.hi[f] = lo.data_ptr(), hi.data_ptr()
+                desc.shared |= (1 << f) if k in shared else 0
+        _lib.check(self._L, self._L.vnl_env_set_domain_ranges(self._env_h, C.byref(desc), self._stream()))
+        self._domain_ranges = ({k: tuple(t.clone() for t in v) for k, v in bounds.items()}, tuple(shared))
+
+    def _with_domains(self, tables, body_tables, ranges="carry") -> "RodentTracking":
+        """A new env of this configuration and num_envs with the given parts of a domain (already validated; None: unset);
+        the ranges of this env are carried over unless others are given."""
         new = object.__new__(type(self))
         new.__dict__.update(self._config_attrs)
         new._build(self._build_args[0], self.num_envs, *self._build_args[1:])
@@ -220,7 +253,90 @@ class RodentTracking(Env):
                 raise ValueError(new._L.vnl_last_error().decode())
             _lib.check(new._L, rc)
             new._body_domain = dict(body_tables)
+        ranges = self._domain_ranges if isinstance(ranges, str) else ranges
+        if ranges is not None:
+            new._set_domain_ranges(ranges)
         return new
+
+    def with_domain_ranges(self, ranges: Mapping[str, Any], shared: Sequence[str] = ()) -> "RodentTracking":
+        """A NEW env of the same model, clip, parameters and num_envs whose envs get a new physical domain per EPISODE
+        (include/vnl.h: vnl_env_set_domain_ranges): `reset_done` -- the fresh auto-reset -- draws the fields in `ranges` anew
+        for every env it resets, inside the reset kernel, and `redraw_domain` does so on request (the first episode).
+
+          ranges  {field: (lo, hi)} with the field names of `with_domain`; lo / hi are scalars or arrays of the field's
+                  length: ABSOLUTE bounds per element (`domain_ranges_scaled` builds them from multiples of the compiled values)
+          shared  names of fields of `ranges` that take ONE uniform per (env, episode) for all their elements (every geom's
+                  friction scaled alike), instead of one per element
+
+        A field left out is never redrawn.  Domains of this env (with_domain, with_body_domain) are carried over: the tables
+        keep those values until an env's first redraw; the body domain is never redrawn.  `with_domain` /
+        `with_body_domain` of the result carry the ranges, `with_num_envs` carries the ranges but not the tables.  Raises
+        ValueError on an unknown field, a wrong length, or bad bounds (non-finite, lo > hi, friction lo <= 0, damping or
+        armature lo < 0)."""
+        d, bounds = self.dims, {}
+        for k, v in dict(ranges).items():
+            if k not in DOMAIN_FIELDS:
+                raise ValueError(f"unknown domain field {k!r}: expected some of {sorted(DOMAIN_FIELDS)}")
+            dim, least, closed = DOMAIN_FIELDS[k]
+            n = int(getattr(d, dim))
+            try:
+                lo, hi = v
+            except (TypeError, ValueError):
+                raise ValueError(f"domain range {k!r} must be a (lo, hi) pair") from None
+            pair = []
+            for name, x in (("lo", lo), ("hi", hi)):
+                t = torch.as_tensor(x).detach().to(dtype=torch.float64, device="cpu")
+                if t.dim() == 0:
+                    t = t.expand(n)
+                if tuple(t.shape) != (n,):
+                    raise ValueError(f"domain range {k!r}: {name} must be a scalar or have shape ({n},), got {tuple(t.shape)}")
+                if not bool(torch.isfinite(t).all()):
+                    raise ValueError(f"domain range {k!r}: {name} has non-finite values")
+                pair.append(t.contiguous().clone())
+            if not bool((pair[0] <= pair[1]).all()):
+                raise ValueError(f"domain range {k!r}: lo must not exceed hi")
+            if least is not None and not bool(((pair[0] >= least) if closed else (pair[0] > least)).all()):
+                raise ValueError(f"domain range {k!r}: lo must be {'>=' if closed else '>'} {least}")
+            bounds[k] = tuple(pair)
+        shared = tuple(shared)
+        for k in shared:
+            if k not in bounds:
+                raise ValueError(f"shared field {k!r} has no range")
+        return self._with_domains(self._domain, self._body_domain, ranges=(bounds, shared))
+
+    @property
+    def domain_ranges(self) -> Optional[Dict[str, Any]]:
+        """{field: (lo, hi) float64 (n,) tensors} of `with_domain_ranges` plus "shared": the shared field names; or None."""
+        if self._domain_ranges is None:
+            return None
+        bounds, shared = self._domain_ranges
+        return dict({k: tuple(t.clone() for t in v) for k, v in bounds.items()}, shared=tuple(shared))
+
+    def redraw_domain(self, *, seed: int, step_base, step_offset: int = 0, env_offset: int = 0,
+                      mask: Optional[torch.Tensor] = None, initial: bool = False) -> None:
+        """The domain of the envs whose `mask` (B,) is nonzero (None: every env) drawn anew from this env's ranges, in place
+        (vnl_env_redraw_domain): the draw `reset_done` makes for the envs it resets, keyed by (seed, step_base[0] +
+        step_offset, env_offset + env index) -- ppo_imitation/philox.py domain_draws -- as a launch of its own.
+        `initial=True` draws from a block range of its own: the domain of a FIRST episode differs from that of a reset at the
+        same counter.  `step_base`: int64 [1] on the env's device (only read), or an int.  ValueError without ranges."""
+        if self._domain_ranges is None:
+            raise ValueError("redraw_domain: this env has no domain ranges (with_domain_ranges)")
+        B = self.num_envs
+        if not isinstance(step_base, torch.Tensor):
+            step_base = torch.tensor([int(step_base)], dtype=torch.int64, device=self.device)
+        if step_base.dtype != torch.int64 or step_base.numel() != 1 or step_base.device != self.device:
+            raise ValueError("step_base must be an int or an int64 tensor of one element on the env's device")
+        mk = None
+        if mask is not None:
+            if tuple(mask.shape) != (B,):
+                raise ValueError(f"mask must be ({B},), got {tuple(mask.shape)}")
+            mk = mask.to(device=self.device, dtype=torch.float32).contiguous()
+        nz = _lib.ResetNoise()
+        nz.seed, nz.step_base = int(seed) & 0xFFFFFFFFFFFFFFFF, step_base.data_ptr()
+        nz.step_offset, nz.env_offset = int(step_offset), int(env_offset)
+        _lib.check(self._L, self._L.vnl_env_redraw_domain(self._env_h, None if mk is None else mk.data_ptr(), C.byref(nz),
+                                                          int(bool(initial)), self._stream()))
+        self._hold = (mk, step_base)
 
     def with_domain(self, domain: Mapping[str, Any]) -> "RodentTracking":
         """A NEW env of the same model, clip, parameters and num_envs whose envs each run with their own values of the raw
@@ -231,7 +347,8 @@ class RodentTracking(Env):
           dof_damping, dof_armature  (num_envs, nv)
 
         A field left out keeps the model's value.  Derived constants (invweight0, meaninertia) stay as compiled; the contact
-        rows' inverse weight follows friction.  Values are fixed for the env's lifetime (auto-reset keeps them).  Neither this
+        rows' inverse weight follows friction.  Values are fixed for the env's lifetime (auto-reset keeps them) unless the env
+        has ranges (with_domain_ranges: carried over by this call, a fresh reset then redraws the env's domain).  Neither this
         env nor its CompiledModel is changed.  A body domain of this env (with_body_domain) is carried over.  `with_num_envs`
         of the result carries NO domain: an eval env is randomised by a call of its own.  Raises ValueError on an unknown
         field, a wrong shape or a bad value (non-finite, friction <= 0, damping or armature < 0)."""
@@ -309,6 +426,27 @@ class RodentTracking(Env):
             ct = C.c_double if self._dtype == torch.float64 else C.c_float
             flat = torch.from_numpy(np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(total,)).copy())
         return flat.view(self.num_envs, cnt.value)
+
+    def _copy_domain_tables(self, saved: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The five four-field tables as one flat tensor on the env's device (they are one allocation, "dom_mu" first), or --
+        given such a tensor -- written back: a caller that runs fresh resets it must not keep (the warm-up of a graph
+        capture) puts a redrawn domain back with this.  Synchronous."""
+        ptr, cnt = C.c_void_p(), C.c_int32()
+        _lib.check(self._L, self._L.vnl_env_scratch(self._env_h, b"dom_mu", C.byref(ptr), C.byref(cnt)))
+        d = self.dims
+        total = self.num_envs * (2 * int(d.ngeom_collide) + int(d.nu) + 2 * int(d.nv))
+        flat = saved if saved is not None else torch.empty(total, dtype=self._dtype, device=self.device)
+        assert flat.numel() == total and flat.dtype == self._dtype and flat.is_contiguous()
+        nbytes = C.c_size_t(flat.element_size() * total)
+        src, dst = (C.c_void_p(flat.data_ptr()), ptr) if saved is not None else (ptr, C.c_void_p(flat.data_ptr()))
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+            rc = C.CDLL("libamdhip64.so").hipMemcpy(dst, src, nbytes, C.c_int(3))
+            if rc != 0:
+                raise _lib.VnlError(f"hipMemcpy failed: {rc}")
+        else:
+            C.memmove(dst, src, nbytes)
+        return flat
 
     def __del__(self):
         try:

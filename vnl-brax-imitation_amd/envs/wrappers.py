@@ -92,6 +92,9 @@ class AutoResetWrapper(Wrapper):
     With `start_priority` (envs/start_priority.py StartPriority; mode="fresh" only) start frame and clip are drawn from its
     table and the episodes that end are counted into its counters -- not those an EpisodeWrapper below truncated.  The
     caller runs its `update()` (between unrolls).
+    An env with domain ranges (`with_domain_ranges`; mode="fresh" only has a use for them) gets a new physical domain with
+    every fresh reset -- the reset kernel reads the ranges from the env, no argument here -- and `reset` draws the domain of
+    every env's FIRST episode (`redraw_domain(initial=True)` at this wrapper's seed, the counter's value and env_offset).
     """
 
     def __init__(self, env: Env, reset_info_on_autoreset: bool = False, mode: str = "first_state", seed: int = 0,
@@ -108,11 +111,22 @@ class AutoResetWrapper(Wrapper):
         self.reset_info, self.start_priority = reset_info_on_autoreset, start_priority
         self.mode, self.seed, self.env_offset = mode, int(seed), int(env_offset)
 
-    def reset(self, rng=None, **kw) -> State:
-        state = self.env.reset(rng, **kw)
+    def reset(self, rng=None, *, reset_step=None, **kw) -> State:
+        """`reset_step` (mode="fresh"): the value the counter starts from, an int or int64 [1] tensor -- a resumed run's;
+        default 0."""
         if self.mode == "fresh":
-            state.info["reset_step"] = torch.zeros(1, dtype=torch.int64, device=state.obs.device)
+            base = self.env.unwrapped
+            counter = torch.zeros(1, dtype=torch.int64, device=base.device)
+            if reset_step is not None:
+                counter.copy_(torch.as_tensor(reset_step, dtype=torch.int64).reshape(1))
+            if getattr(base, "domain_ranges", None) is not None:  # the first episodes are randomised too: before their reset
+                base.redraw_domain(seed=self.seed, step_base=counter, env_offset=self.env_offset, initial=True)
+            state = self.env.reset(rng, **kw)
+            state.info["reset_step"] = counter
             return state
+        if reset_step is not None:
+            raise ValueError("reset_step has no meaning without mode='fresh'")
+        state = self.env.reset(rng, **kw)
         state.info["first_pipeline_state"] = state.pipeline_state.clone()
         state.info["first_obs"] = state.obs.clone()
         if self.reset_info:
@@ -182,7 +196,7 @@ class EvalWrapper(Wrapper):
 
 def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None,
          reset_info_on_autoreset: bool = False, auto_reset: str = "first_state", auto_reset_seed: int = 0,
-         env_offset: int = 0, start_priority=None) -> Wrapper:
+         env_offset: int = 0, start_priority=None, domain_ranges=None, domain_shared=()) -> Wrapper:
     """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
 
     `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
@@ -193,7 +207,15 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
     `auto_reset`: "first_state" (brax: a done env returns to the cached first state) or "fresh" (a new start frame, clip
     and reset noise per episode, drawn on the device; AutoResetWrapper), with `auto_reset_seed` and `env_offset` (the global
     index of this batch's env 0, for sharded runs) keying the draws.  `start_priority`: with "fresh", a StartPriority
-    (envs/start_priority.py) whose table the draws follow and whose counters the resets feed."""
+    (envs/start_priority.py) whose table the draws follow and whose counters the resets feed.
+
+    `domain_ranges` ({field: (lo, hi)}, `domain_shared`: `env.with_domain_ranges`), with "fresh" only: every fresh reset draws
+    the env's physical domain anew inside the reset kernel, and the wrapper's `reset` draws that of the first episodes.
+    Applied after `randomization_fn`, whose values an env keeps until its first redraw."""
+    if domain_ranges is not None and auto_reset != "fresh":
+        raise ValueError("domain_ranges needs auto_reset='fresh': the cached first state belongs to one domain")
+    if domain_ranges is None and tuple(domain_shared):
+        raise ValueError("domain_shared without domain_ranges")
     if randomization_fn is not None:
         if not hasattr(env, "with_domain"):
             raise ValueError(f"{type(env).__name__} has no with_domain: domain randomisation needs a tracking env of this library")
@@ -205,5 +227,9 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
             env = env.with_domain(domain)
         if bodies:
             env = env.with_body_domain(bodies)
+    if domain_ranges is not None:
+        if not hasattr(env, "with_domain_ranges"):
+            raise ValueError(f"{type(env).__name__} has no with_domain_ranges: a domain redraw needs a tracking env of this library")
+        env = env.with_domain_ranges(domain_ranges, shared=domain_shared)
     return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset, mode=auto_reset,
                             seed=auto_reset_seed, env_offset=env_offset, start_priority=start_priority)

@@ -228,6 +228,9 @@ class GraphedUnroll:
         prio = fz[0].start_priority  # (the warm-up's resets must not count either)
         counters = [prio.count_ended, prio.count_failed] if prio is not None else []
         saved_counters = [c.clone() for c in counters]
+        # (.. nor redraw the domain: with ranges the warm-up's fresh resets write the library-owned tables)
+        base = fz[0].unwrapped
+        saved_domain = base._copy_domain_tables() if getattr(base, "domain_ranges", None) is not None else None
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -237,6 +240,8 @@ class GraphedUnroll:
         _restore_state(env_state, saved)
         for c, s0 in zip(counters, saved_counters):
             c.copy_(s0)
+        if saved_domain is not None:
+            base._copy_domain_tables(saved_domain)
         self.graph = torch.cuda.CUDAGraph()
         if dev_noise:
             policy.counter.copy_(gen_state)

@@ -6,7 +6,7 @@
     counter = (block, env, step low 32 bits, (step >> 32) << 2 | stream),  step < 2^62
     stream  = 0 latent draw, 1 action draw, 2 the random action shared by the batch (env = 0xFFFFFFFF),
               3 the fresh episode reset of an env (vnl_env_reset_done): blocks 0.. its reset noise, block 0x80000000 its
-              start frame and clip
+              start frame and clip, blocks 0x40000000.. the redraw of its physical domain (domain_draws)
 
 A call yields four words x0..x3; u_i = ((x_i >> 8) + 0.5) 2^-24 lies strictly inside (0, 1).  Normal draws are Box-Muller
 pairs, (u0, u1) -> sqrt(-2 ln u0) (cos, sin)(2 pi u1) and (u2, u3) likewise; element j of an env's row is output j % 4 of block
@@ -27,6 +27,8 @@ MASK = 0xFFFFFFFF
 STREAM_LATENT, STREAM_ACTION, STREAM_SHARED = 0, 1, 2
 STREAM_RESET = 3  # the last one: the stream field is the low two bits of counter word 3
 RESET_INT_BLOCK = 0x80000000  # the block of stream 3 whose words x0, x1 give start frame and clip
+DOMAIN_BLOCK, DOMAIN_INITIAL, DOMAIN_FIELD_STRIDE = 0x40000000, 0x20000000, 0x00100000  # stream 3: the domain redraw
+DOMAIN_FIELDS = ("cg_friction", "act_gain", "dof_damping", "dof_armature")  # field index f, the order of vnl_domain
 SHARED_ENV = 0xFFFFFFFF  # the env word of stream 2: no env may have this index
 
 IntLike = Union[int, torch.Tensor]
@@ -103,6 +105,33 @@ def reset_draws(seed: int, step: IntLike, env: torch.Tensor, nq: int, start_hi: 
     a = (2.0 * math.pi) * u[..., 1::2]
     nz = torch.stack((r * torch.cos(a), r * torch.sin(a)), dim=-1).reshape(env.shape[0], -1)[:, :nq]
     return below(x[:, 0], int(start_hi)), below(x[:, 1], int(num_clips)), (nz * float(noise_scale)).to(torch.float32)
+
+
+def domain_draws(seed: int, step: IntLike, env: torch.Tensor, field: IntLike, lo, hi, shared: bool = False,
+                 initial: bool = False) -> torch.Tensor:
+    """float64 [len(env), n]: the values a domain redraw (vnl_env_reset_done with ranges, vnl_env_redraw_domain) draws for
+    field `field` (index or name of DOMAIN_FIELDS) of the envs with GLOBAL indices `env` at `step`, between the bounds `lo`,
+    `hi` (float64 [n]).  Element j takes word j % 4 of block DOMAIN_BLOCK + initial * DOMAIN_INITIAL + f * DOMAIN_FIELD_STRIDE
+    + j / 4; a `shared` field word 0 of the first block for every element.  u = (x + 0.5) 2^-32 is exact in float64;
+    v = lo + u * (hi - lo) rounds the difference, the product and the sum separately (torch ops do not fuse them): the bits
+    of the device.  The tables are v cast to the env's real type, the inverse weight `contact_invweight` of v."""
+    f = DOMAIN_FIELDS.index(field) if isinstance(field, str) else int(field)
+    lo = torch.as_tensor(lo, dtype=torch.float64).reshape(-1)
+    hi = torch.as_tensor(hi, dtype=torch.float64).reshape(-1)
+    n = lo.shape[0]
+    assert hi.shape[0] == n and 0 <= f < 4 and n <= 4 * DOMAIN_FIELD_STRIDE
+    block0 = DOMAIN_BLOCK + (DOMAIN_INITIAL if initial else 0) + f * DOMAIN_FIELD_STRIDE
+    x = _words(seed, step, env, 1 if shared else n, STREAM_RESET, block0=block0).reshape(env.shape[0], -1)
+    x = x[:, :1].expand(env.shape[0], n) if shared else x[:, :n]
+    u = (x.to(torch.float64) + 0.5) * 2.0 ** -32
+    w = hi - lo
+    p = u.cpu() * w
+    return lo + p
+
+
+def contact_invweight(t, mu, impratio: float):
+    """The contact rows' inverse weight from friction `mu`, float64, as the library derives it (csrc/vnl_types.h)."""
+    return (t + mu * mu * t) * 2 * mu * mu / impratio
 
 
 def words_u32(t) -> torch.Tensor:

@@ -147,6 +147,8 @@ def train(
     policy_noise: str = "generator",
     auto_reset: str = "first_state",
     start_priority: Any = False,
+    domain_ranges=None,
+    domain_shared=(),
 ):
     """PPO training (train.py:62-491).
 
@@ -190,6 +192,15 @@ def train(
     draws from the same table.  `train.last_start_priority` is the object (checkpoint.save_params(start_priority=
     its state_dict()) / `restore_from` carry table and counters).  The evaluator's env is not prioritised.
 
+    `domain_ranges` ({field: (lo, hi)} absolute bounds, envs/rodent.py with_domain_ranges / domain_ranges_scaled) and
+    `domain_shared`; needs auto_reset="fresh".  A new physical domain per EPISODE for the training envs: every fresh reset
+    draws friction, gain, damping and armature of the env anew inside the reset kernel (vnl_env_set_domain_ranges), the
+    first episodes get theirs at the wrapper's reset; bound after `randomization_fn`, whose values an env keeps until its
+    first redraw.  The draws are keyed like those of the fresh reset (rank * (num_envs // world) + env index): nothing more
+    is needed with several ranks.  The evaluator's env gets the ranges and ONE draw, on the eval seed: its later episodes are
+    not redrawn, as its auto-reset is not fresh (EvalWrapper scores first episodes only).  A checkpoint does not carry the
+    tables: a resumed run resets its envs once more, with the initial draw made at the resumed counter.
+
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
     ~500 launches of microsecond kernels and purely launch-bound.
@@ -225,7 +236,8 @@ def train(
     env = env_wrappers.wrap(environment, episode_length=episode_length, action_repeat=action_repeat,
                             randomization_fn=bind_randomization(randomization_fn, local_envs, seed),
                             reset_info_on_autoreset=reset_info_on_autoreset, auto_reset=auto_reset,
-                            auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs, start_priority=prio)
+                            auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs, start_priority=prio,
+                            domain_ranges=domain_ranges, domain_shared=domain_shared)
     env_state = env.reset(g_env)
 
     normalize = (lambda x, y: x)
@@ -273,6 +285,9 @@ def train(
             training_state.policy_counter.copy_(ck["policy_counter"])
         if training_state.reset_step is not None and "reset_step" in ck:  # (the episode draws go on, not from step 0 again)
             training_state.reset_step.copy_(ck["reset_step"])
+            if domain_ranges is not None:  # (the tables are not in the checkpoint: the initial draw at the resumed counter)
+                env_state = env.reset(g_env, reset_step=ck["reset_step"])
+                training_state.reset_step = env_state.info["reset_step"]
         if prio is not None and "start_priority" in ck:
             prio.load_state_dict(ck["start_priority"])
 
@@ -606,6 +621,11 @@ def train(
         ev_wrapped = env_wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat,
                                        randomization_fn=bind_randomization(randomization_fn, num_eval_envs, seed * 31 + 7),
                                        reset_info_on_autoreset=reset_info_on_autoreset)
+        if domain_ranges is not None:  # one draw on the eval seed; first_state auto-reset keeps it (see the docstring)
+            ev_base = ev_wrapped.unwrapped.with_domain_ranges(domain_ranges, shared=domain_shared)
+            ev_base.redraw_domain(seed=seed * 31 + 7, step_base=0, initial=True)
+            ev_wrapped = env_wrappers.wrap(ev_base, episode_length=episode_length, action_repeat=action_repeat,
+                                           reset_info_on_autoreset=reset_info_on_autoreset)
         evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval, **eval_kw),
                                      num_eval_envs=num_eval_envs, episode_length=episode_length,
                                      action_repeat=action_repeat, key=g_eval)
@@ -628,10 +648,11 @@ def train(
             current_step = training_state.env_steps
             if num_resets_per_eval > 0:
                 reset_step = env_state.info.get("reset_step")
-                env_state = env.reset(g_env)
                 if reset_step is not None:  # (auto_reset="fresh": the draws go on where they were, not from step 0 again)
-                    env_state.info["reset_step"].copy_(reset_step)
+                    env_state = env.reset(g_env, reset_step=reset_step)
                     training_state.reset_step = env_state.info["reset_step"]
+                else:
+                    env_state = env.reset(g_env)
         if rank == 0:
             metrics = training_metrics
             if evaluator is not None:
@@ -655,5 +676,6 @@ def train(
     train.last_training_state = training_state  # value net / optimiser for checkpoint-resume (beyond the reference)
     train.last_ppo_network = ppo_network
     train.last_env_state = env_state  # the training envs as the run leaves them
+    train.last_env = env  # .. and the wrapped env they belong to (its `unwrapped` holds the per-env domain tables)
     train.last_start_priority = prio  # the StartPriority of the run (None without start_priority)
     return make_policy, params, metrics
