@@ -31,6 +31,12 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          pivot block writing V = U / D and 1/D1 inside the step chain and its lane sets reading their lines one after the
 #          other, the solver's qg1 / qg2 / Gauss scalars in per-dof passes of their own (regression build and bisecting tool:
 #          the same operations in another order of issue, the same bits on every output; tests/test_gpu_lds_chain.py)
+#   sgprplain -DVNL_SGPR_PLAIN: the lane predicates of a substep as the compiler used to carry them -- `u < n` of blk_apply's
+#          selects, the debug trace's literal row addresses and the masks lane < 64 / lane > 63 of every one-trip region found
+#          loop-invariant, hoisted to the top of the kernel, parked in VGPR lanes for want of SGPRs and read back with
+#          v_readlane at every use (regression build for VNL_LOCAL / VNL_ROLLED / VNL_LANE_RANGE of csrc/vnl_body.h: the same
+#          compares on the same operands issued in another place or not needed, the same bits on every output;
+#          tests/test_gpu_sgpr_plain.py, tools/spill_report.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -46,6 +52,7 @@ VARIANTS = {
     "plain": ("libvnl_plain.so", ["-DVNL_SOLVER_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "vmemplain": ("libvnl_vmemplain.so", ["-DVNL_VMEM_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "ldsplain": ("libvnl_ldsplain.so", ["-DVNL_LDS_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "sgprplain": ("libvnl_sgprplain.so", ["-DVNL_SGPR_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

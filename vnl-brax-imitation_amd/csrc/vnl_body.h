@@ -304,6 +304,32 @@ VNL_HD S6 mcross_force(S6 v, S6 f) { return S6{cross(v.a, f.a) + cross(v.l, f.l)
 #else
 #define VNL_OPAQUE(x) (void)(x)
 #endif
+// A per-lane value made opaque WHERE IT IS USED, so that what is computed from it -- a compare against a constant, the lane
+// predicate of a select -- is computed there, in two instructions, and not found loop-invariant, hoisted to the top of the
+// kernel into an SGPR pair, parked in VGPR lanes for want of SGPRs and fetched back with two v_readlane and a wait state at
+// every use.  Same value, same select: the same bits on every output.  A macro of its own (VNL_PIN is off under
+// -DVNL_VMEM_PLAIN); -DVNL_SGPR_PLAIN (csrc/build.py --sgprplain) keeps the former forms.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_SGPR_PLAIN)
+#define VNL_LOCAL(x) asm volatile("" : "+v"(x))
+#else
+#define VNL_LOCAL(x) (void)(x)
+#endif
+// A wave-uniform walk over LDS kept as a LOOP: unrolled, each of its literal addresses becomes an SGPR of its own (LDS base
+// + offset, one s_add each), hoisted to the top of the kernel and parked in a VGPR lane -- the debug trace's walk over the
+// constraint rows alone took 156 lanes of three VGPRs and as many writes at every launch, traced or not.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_SGPR_PLAIN)
+#define VNL_ROLLED _Pragma("nounroll")
+#else
+#define VNL_ROLLED
+#endif
+// The compiler is TOLD that a workgroup is one wave: it does not derive lane < 64 from __launch_bounds__(64) before its loop
+// passes run, so every `for (l = lane; l < 64; ...)` trip kept the two masks lane < 64 and lane > 63 -- loop-invariant,
+// hoisted, parked in VGPR lanes, read back as exec masks in front of every such region.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_SGPR_PLAIN)
+#define VNL_LANE_RANGE(lane) __builtin_assume((lane) < (unsigned)VNL_LANES)
+#else
+#define VNL_LANE_RANGE(lane) (void)(lane)
+#endif
 // Per-lane constants of the solve phase held in REGISTERS (device code; the host simulation reads the tables where they are,
 // and so does the regression build -DVNL_SOLVER_PLAIN, csrc/build.py --plain: today's form of everything the solver loop used
 // to fetch from global memory -- same values, so the same bits on every output)
@@ -1704,7 +1730,8 @@ struct EnvWaveT {
 #pragma unroll
         for (int k = 0; k < PH; k++) {  // (3)
           if (t0 + k >= trips) break;
-          const int n = (int)(d[k] >> 16) & 15;
+          int n = (int)(d[k] >> 16) & 15;
+          VNL_LOCAL(n);
           vreal p0 = vreal(0.), p1 = vreal(0.);
 #pragma unroll
           for (int u = 0; u < W; u++) {
@@ -2044,8 +2071,10 @@ struct EnvWaveT {
     VNL_SYNC();
     if (trace) {  // debug trace: which rows exist (the pre-solver discrete decisions)
       VNL_SERIAL {
+        VNL_ROLLED
         for (int w = 0; w < 16; w++) {
           int bits = 0;
+          VNL_ROLLED
           for (int b = 0; b < 32; b++) {
             const int r = 32 * w + b;
             if (r < MI(nefc) && s[LO(efc_D) + r] != vreal(0.)) bits |= 1 << b;
@@ -3210,6 +3239,7 @@ struct EnvWaveT {
   // RodentTracking.step, rodent.py:178-239 (HumanoidTracking.step, humanoid.py:185-239, by the env flags)
   // dump_mid / trace_base: debug only (vnl_env_debug), null in normal use
   VNL_HD void step(const vreal* action, vreal* dump_mid, int* trace_base) const {
+    VNL_LANE_RANGE(lane);
     prof_begin();
     int clip = st.clip_id[e], old_frame = st.cur_frame[e], old_sub = st.sub_clip_frame[e];
     load_tables();
