@@ -37,6 +37,11 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          v_readlane at every use (regression build for VNL_LOCAL / VNL_ROLLED / VNL_LANE_RANGE of csrc/vnl_body.h: the same
 #          compares on the same operands issued in another place or not needed, the same bits on every output;
 #          tests/test_gpu_sgpr_plain.py, tools/spill_report.py)
+#   xlaneplain -DVNL_XLANE_PLAIN: the cross-lane glue of a substep as it was -- every row_bcast step of a wave sum or scan as
+#          the builtin with old = 0 and an add (v_mov_b32 0, v_mov_b32_dpp, v_add_f32) instead of one masked v_add_f32_dpp, every
+#          sum and scan a sequence of its own, the last trip of dof_prefix (nine dofs of the rodent's 73) as six full scans
+#          (regression build for vnl_rows_join / VNL_WAVE_SUMS / VNL_SCAN6 and dof_prefix's tail form of csrc/vnl_body.h: the
+#          same adds on the same operands, the same bits on every output; tests/test_gpu_xlane_plain.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 VARIANTS = {
@@ -53,6 +58,7 @@ VARIANTS = {
     "vmemplain": ("libvnl_vmemplain.so", ["-DVNL_VMEM_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "ldsplain": ("libvnl_ldsplain.so", ["-DVNL_LDS_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     "sgprplain": ("libvnl_sgprplain.so", ["-DVNL_SGPR_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "xlaneplain": ("libvnl_xlaneplain.so", ["-DVNL_XLANE_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
     # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
     "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
 }

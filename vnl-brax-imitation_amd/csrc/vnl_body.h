@@ -70,6 +70,85 @@
 // row_half_mirror, row_mirror: every lane then holds its row's total), the row totals combined by row_bcast:15 (rows 1, 3
 // take rows 0, 2) and row_bcast:31 (row 3 takes rows 0+1), the grand total read from lane 63: 6 DPP adds + 1 v_readlane.
 // Every lane returns the same value.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VNL_XLANE_PLAIN)
+// The two steps that cross rows, one instruction each.  Written with the builtin (old = 0, a row mask, then an add) a row_bcast
+// step compiles to three -- v_mov_b32 tmp, 0; v_mov_b32_dpp tmp, x; v_add_f32 -- because the compiler folds a DPP move into
+// its user only where every lane is written; here the add itself carries the control and the row mask, and the rows outside
+// the mask are simply not written.  They therefore keep x where the former form computed x + 0.0: a -0.0 there stays -0.0
+// instead of becoming +0.0, and nothing else differs.  No caller can see it but the carry-less scan (VNL_SCAN_ADD, VNL_SCAN6:
+// the contact-wrench prefix of constraint_force, whose entries are only ever subtracted from each other): a sum reads lane 63,
+// which both steps write, and a carried scan adds its carry, +0.0 or non-zero, afterwards.
+// The statements are not volatile (dead ones go, the scheduler may move them) and model nothing for the compiler, so the wait
+// states a DPP read of a VGPR that a VALU instruction has just written needs (two) stand inside the string: `s_nop 1` in front
+// of the first step, whose operands the in-row steps before the statement may have written in the instruction before, and
+// between the two stages whatever the other values of the statement do not already put there (n values: n - 1 instructions
+// between a value's two steps).  -DVNL_XLANE_PLAIN (csrc/build.py --xlaneplain) keeps every former form.
+#define VNL_XLANE 1
+#define VNL_B15_(n) "v_add_f32_dpp %" #n ", %" #n ", %" #n " row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+#define VNL_B31_(n) "v_add_f32_dpp %" #n ", %" #n ", %" #n " row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+VNL_HD void vnl_rows_join(float& a) { asm("s_nop 1\n\t" VNL_B15_(0) "s_nop 1\n\t" VNL_B31_(0) : "+v"(a)); }
+VNL_HD void vnl_rows_join(float& a, float& b) {
+  asm("s_nop 1\n\t" VNL_B15_(0) VNL_B15_(1) "s_nop 0\n\t" VNL_B31_(0) VNL_B31_(1) : "+v"(a), "+v"(b));
+}
+VNL_HD void vnl_rows_join(float& a, float& b, float& c) {
+  asm("s_nop 1\n\t" VNL_B15_(0) VNL_B15_(1) VNL_B15_(2) VNL_B31_(0) VNL_B31_(1) VNL_B31_(2) : "+v"(a), "+v"(b), "+v"(c));
+}
+VNL_HD void vnl_rows_join(float& a, float& b, float& c, float& d) {
+  asm("s_nop 1\n\t" VNL_B15_(0) VNL_B15_(1) VNL_B15_(2) VNL_B15_(3) VNL_B31_(0) VNL_B31_(1) VNL_B31_(2) VNL_B31_(3)
+      : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+VNL_HD void vnl_rows_join(float& a, float& b, float& c, float& d, float& e, float& f) {
+  asm("s_nop 1\n\t" VNL_B15_(0) VNL_B15_(1) VNL_B15_(2) VNL_B15_(3) VNL_B15_(4) VNL_B15_(5)
+      VNL_B31_(0) VNL_B31_(1) VNL_B31_(2) VNL_B31_(3) VNL_B31_(4) VNL_B31_(5)
+      : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+}
+VNL_HD void vnl_rows_join(float& a, float& b, float& c, float& d, float& e, float& f, float& g, float& h, float& i) {
+  asm("s_nop 1\n\t" VNL_B15_(0) VNL_B15_(1) VNL_B15_(2) VNL_B15_(3) VNL_B15_(4) VNL_B15_(5) VNL_B15_(6) VNL_B15_(7) VNL_B15_(8)
+      VNL_B31_(0) VNL_B31_(1) VNL_B31_(2) VNL_B31_(3) VNL_B31_(4) VNL_B31_(5) VNL_B31_(6) VNL_B31_(7) VNL_B31_(8)
+      : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i));
+}
+#undef VNL_B15_
+#undef VNL_B31_
+// the xor-butterfly inside each row of 16 lanes: every lane then holds its row's total
+VNL_HD float vnl_row_sum(float x) {
+#define VNL_DPP_STEP(ctrl) x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
+  VNL_DPP_STEP(0xB1);   // quad_perm [1,0,3,2]
+  VNL_DPP_STEP(0x4E);   // quad_perm [2,3,0,1]
+  VNL_DPP_STEP(0x141);  // row_half_mirror
+  VNL_DPP_STEP(0x140);  // row_mirror
+#undef VNL_DPP_STEP
+  return x;
+}
+VNL_HD float vnl_last_lane(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63)); }
+VNL_HD float vnl_wave_sum(float x) {
+  x = vnl_row_sum(x);
+  vnl_rows_join(x);
+  return vnl_last_lane(x);
+}
+// .. of several values at once: the same adds for each, the row-crossing stage shared (one s_nop 1 for all of them)
+VNL_HD void vnl_wave_sums(float& a, float& b) {
+  a = vnl_row_sum(a), b = vnl_row_sum(b);
+  vnl_rows_join(a, b);
+  a = vnl_last_lane(a), b = vnl_last_lane(b);
+}
+VNL_HD void vnl_wave_sums(float& a, float& b, float& c) {
+  a = vnl_row_sum(a), b = vnl_row_sum(b), c = vnl_row_sum(c);
+  vnl_rows_join(a, b, c);
+  a = vnl_last_lane(a), b = vnl_last_lane(b), c = vnl_last_lane(c);
+}
+VNL_HD void vnl_wave_sums(float& a, float& b, float& c, float& d) {
+  a = vnl_row_sum(a), b = vnl_row_sum(b), c = vnl_row_sum(c), d = vnl_row_sum(d);
+  vnl_rows_join(a, b, c, d);
+  a = vnl_last_lane(a), b = vnl_last_lane(b), c = vnl_last_lane(c), d = vnl_last_lane(d);
+}
+VNL_HD void vnl_wave_sums(float& a, float& b, float& c, float& d, float& e, float& f, float& g, float& h, float& i) {
+  a = vnl_row_sum(a), b = vnl_row_sum(b), c = vnl_row_sum(c), d = vnl_row_sum(d), e = vnl_row_sum(e);
+  f = vnl_row_sum(f), g = vnl_row_sum(g), h = vnl_row_sum(h), i = vnl_row_sum(i);
+  vnl_rows_join(a, b, c, d, e, f, g, h, i);
+  a = vnl_last_lane(a), b = vnl_last_lane(b), c = vnl_last_lane(c), d = vnl_last_lane(d), e = vnl_last_lane(e);
+  f = vnl_last_lane(f), g = vnl_last_lane(g), h = vnl_last_lane(h), i = vnl_last_lane(i);
+}
+#else
 VNL_HD float vnl_wave_sum(float x) {
 #define VNL_DPP_STEP(ctrl) x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
   VNL_DPP_STEP(0xB1);   // quad_perm [1,0,3,2]
@@ -81,6 +160,7 @@ VNL_HD float vnl_wave_sum(float x) {
   x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x143, 0xc, 0xf, false));  // row_bcast:31
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
 }
+#endif
 // .. of values that are zero outside the first 16 lanes (the line search when at most 16 constraint rows exist, one per lane): the
 // butterfly inside the first row of 16 is the whole sum -- 4 DPP adds + 1 v_readlane
 VNL_HD float vnl_wave_sum16(float x) {
@@ -95,6 +175,29 @@ VNL_HD float vnl_wave_sum16(float x) {
 VNL_HD bool vnl_wave_any(bool x) { return __ballot(x) != 0ull; }
 // inclusive prefix sum over the 64 lanes: Hillis-Steele inside each row of 16 (row_shr 1, 2, 4, 8), then the row
 // totals are carried over with row_bcast:15 (rows 1, 3) and row_bcast:31 (rows 2, 3)
+#ifdef VNL_XLANE
+// (Hillis-Steele inside each row of 16: these four the compiler folds into single v_add_f32_dpp itself)
+VNL_HD float vnl_row_scan(float x) {
+#define VNL_DPP_SCAN(ctrl) \
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, false))
+  VNL_DPP_SCAN(0x111);  // row_shr:1
+  VNL_DPP_SCAN(0x112);  // row_shr:2
+  VNL_DPP_SCAN(0x114);  // row_shr:4
+  VNL_DPP_SCAN(0x118);  // row_shr:8
+#undef VNL_DPP_SCAN
+  return x;
+}
+VNL_HD float vnl_wave_scan(float x) {
+  x = vnl_row_scan(x);
+  vnl_rows_join(x);  // row_bcast:15 -> rows 1 and 3, row_bcast:31 -> rows 2 and 3
+  return x;
+}
+// .. of the six components of a spatial vector, the row-crossing stage shared
+VNL_HD void vnl_wave_scan6(float& a, float& b, float& c, float& d, float& e, float& f) {
+  a = vnl_row_scan(a), b = vnl_row_scan(b), c = vnl_row_scan(c), d = vnl_row_scan(d), e = vnl_row_scan(e), f = vnl_row_scan(f);
+  vnl_rows_join(a, b, c, d, e, f);
+}
+#else
 VNL_HD float vnl_wave_scan(float x) {
 #define VNL_DPP_SCAN(ctrl, rmask) \
   x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rmask, 0xf, false))
@@ -107,6 +210,7 @@ VNL_HD float vnl_wave_scan(float x) {
 #undef VNL_DPP_SCAN
   return x;
 }
+#endif
 #define VNL_SCAN_ADD(x, run) (x = vnl_wave_scan(x)) /* x <- sum over items <= this one (run: host simulation only) */
 #define VNL_WAVE_ITEMS(n) VNL_LANES              /* trip count of a region in which every lane takes part in a scan */
 #define VNL_PAD_ITEMS(n) (((n) + VNL_LANES - 1) / VNL_LANES * VNL_LANES) /* .. over several trips */
@@ -159,6 +263,37 @@ VNL_HD float vnl_recip(float x) {
   float r = __builtin_amdgcn_rcpf(x);
   return r * (2.0f - x * r);
 }
+#endif
+
+// Several sums / the six scans of a spatial vector at once.  On the device the values go through the row-crossing stage of
+// vnl_rows_join together; everywhere else (the host simulation, -DVNL_XLANE_PLAIN) they are the single forms one after the
+// other.  The same adds on the same operands either way.
+#ifdef VNL_XLANE
+#define VNL_WAVE_SUMS(...) vnl_wave_sums(__VA_ARGS__)
+#define VNL_SCAN6(v, run) vnl_wave_scan6(v.a.x, v.a.y, v.a.z, v.l.x, v.l.y, v.l.z)
+#define VNL_SCAN6_C(v, run, cy)                                                          \
+  do {                                                                                      \
+    vnl_wave_scan6(v.a.x, v.a.y, v.a.z, v.l.x, v.l.y, v.l.z);                               \
+    v.a = v.a + cy.a, v.l = v.l + cy.l;                                               \
+    cy.a = v3(vnl_last_lane(v.a.x), vnl_last_lane(v.a.y), vnl_last_lane(v.a.z));         \
+    cy.l = v3(vnl_last_lane(v.l.x), vnl_last_lane(v.l.y), vnl_last_lane(v.l.z));         \
+  } while (0)
+#else
+#define VNL_SUM1_(x) (x = vnl_wave_sum(x))
+#define VNL_SUMS_2_(a, b) (VNL_SUM1_(a), VNL_SUM1_(b))
+#define VNL_SUMS_3_(a, b, c) (VNL_SUM1_(a), VNL_SUM1_(b), VNL_SUM1_(c))
+#define VNL_SUMS_4_(a, b, c, d) (VNL_SUM1_(a), VNL_SUM1_(b), VNL_SUM1_(c), VNL_SUM1_(d))
+#define VNL_SUMS_9_(a, b, c, d, e, f, g, h, i) (VNL_SUMS_4_(a, b, c, d), VNL_SUMS_4_(e, f, g, h), VNL_SUM1_(i))
+#define VNL_SUMS_PICK_(a, b, c, d, e, f, g, h, i, name, ...) name
+#define VNL_WAVE_SUMS(...) \
+  VNL_SUMS_PICK_(__VA_ARGS__, VNL_SUMS_9_, x, x, x, x, VNL_SUMS_4_, VNL_SUMS_3_, VNL_SUMS_2_, x)(__VA_ARGS__)
+#define VNL_SCAN6(v, run)                                                                                    \
+  (VNL_SCAN_ADD(v.a.x, run.a.x), VNL_SCAN_ADD(v.a.y, run.a.y), VNL_SCAN_ADD(v.a.z, run.a.z),                 \
+   VNL_SCAN_ADD(v.l.x, run.l.x), VNL_SCAN_ADD(v.l.y, run.l.y), VNL_SCAN_ADD(v.l.z, run.l.z))
+#define VNL_SCAN6_C(v, run, cy)                                                                           \
+  (VNL_SCAN_ADD_C(v.a.x, run.a.x, cy.a.x), VNL_SCAN_ADD_C(v.a.y, run.a.y, cy.a.y),                     \
+   VNL_SCAN_ADD_C(v.a.z, run.a.z, cy.a.z), VNL_SCAN_ADD_C(v.l.x, run.l.x, cy.l.x),                     \
+   VNL_SCAN_ADD_C(v.l.y, run.l.y, cy.l.y), VNL_SCAN_ADD_C(v.l.z, run.l.z, cy.l.z))
 #endif
 
 // ---- prioritised start frames (include/vnl.h: vnl_start_priority; EnvWaveT::reset_fresh) ----
@@ -735,7 +870,8 @@ struct EnvWaveT {
       s[o + 6] = r.x * mass, s[o + 7] = r.y * mass, s[o + 8] = r.z * mass, s[o + 9] = mass;
     }
     if (with_com) {
-      vreal cx = vnl_wave_sum(csum.x), cy = vnl_wave_sum(csum.y), cz = vnl_wave_sum(csum.z);
+      vreal cx = csum.x, cy = csum.y, cz = csum.z;
+      VNL_WAVE_SUMS(cx, cy, cz);
       VNL_SERIAL { st3(LO(com), v3(cx * total_mass_inv(), cy * total_mass_inv(), cz * total_mass_inv())); }
     }
     VNL_SYNC();
@@ -1854,9 +1990,7 @@ struct EnvWaveT {
           }
         }
       }
-      VNL_SCAN_ADD_C(acc.a.x, run.a.x, carry.a.x), VNL_SCAN_ADD_C(acc.a.y, run.a.y, carry.a.y);
-      VNL_SCAN_ADD_C(acc.a.z, run.a.z, carry.a.z), VNL_SCAN_ADD_C(acc.l.x, run.l.x, carry.l.x);
-      VNL_SCAN_ADD_C(acc.l.y, run.l.y, carry.l.y), VNL_SCAN_ADD_C(acc.l.z, run.l.z, carry.l.z);
+      VNL_SCAN6_C(acc, run, carry);
       if (b < MI(nbody)) st6(QB + 6 * (b + 1), acc);
       if (b == 0) st6(QB, S6{v3(0, 0, 0), v3(0, 0, 0)});
     }
@@ -2088,15 +2222,55 @@ struct EnvWaveT {
   // Q[k] = sum_{d<k} cdof_d * vec_d, k = 0 .. nv (6 floats each): a wave scan carried across the trips
   VNL_HD void dof_prefix(int vec, int Q) const {
     S6 run = S6{v3(0, 0, 0), v3(0, 0, 0)}, carry = run;
-    VNL_FOR(d, VNL_PAD_ITEMS(MI(nv))) {  // every lane takes part in the scans of every trip
+#ifdef VNL_XLANE
+    // A last trip of at most 16 dofs (the rodent: 9 of its 73) is not worth six full scans over one quarter-filled row: see
+    // below.  A constant in the specialised kernels, a wave-uniform branch in the generic ones; never with nv <= 64.
+    const int last = (MI(nv) - 1) / VNL_LANES * VNL_LANES, rem = MI(nv) - last;
+    const bool tail = last > 0 && rem <= 16;
+    const int full = tail ? last : VNL_PAD_ITEMS(MI(nv));
+#else
+    const int full = VNL_PAD_ITEMS(MI(nv));
+#endif
+    VNL_FOR(d, full) {  // every lane takes part in the scans of every trip
       S6 x = S6{v3(0, 0, 0), v3(0, 0, 0)};
       if (d < MI(nv)) x = ld6(LO(cdof) + 6 * d) * s[vec + d];
-      VNL_SCAN_ADD_C(x.a.x, run.a.x, carry.a.x), VNL_SCAN_ADD_C(x.a.y, run.a.y, carry.a.y);
-      VNL_SCAN_ADD_C(x.a.z, run.a.z, carry.a.z), VNL_SCAN_ADD_C(x.l.x, run.l.x, carry.l.x);
-      VNL_SCAN_ADD_C(x.l.y, run.l.y, carry.l.y), VNL_SCAN_ADD_C(x.l.z, run.l.z, carry.l.z);
+#ifdef VNL_XLANE
+      // (the products rounded, as the two-trip loop left them behind its `d < nv` branch: with a single full trip the branch is
+      // gone in the specialised kernels and the compiler otherwise contracts each product into the scan's first add)
+      VNL_OPAQUE(x.a.x);
+      VNL_OPAQUE(x.a.y);
+      VNL_OPAQUE(x.a.z);
+      VNL_OPAQUE(x.l.x);
+      VNL_OPAQUE(x.l.y);
+      VNL_OPAQUE(x.l.z);
+#endif
+      VNL_SCAN6_C(x, run, carry);
       if (d < MI(nv)) st6(Q + 6 * (d + 1), x);
       if (d == 0) st6(Q, S6{v3(0, 0, 0), v3(0, 0, 0)});
     }
+#ifdef VNL_XLANE
+    if (tail) {
+      // The tail trip as two in-row scans: lane 16 k + t takes component c of dof last + t, c = k in the first scan (rows
+      // 0 .. 3) and 4 + k in the second (rows 0, 1).  Lanes 0 .. rem - 1 of a row see exactly the adds that the same lanes of
+      // row 0 saw in the six-scan form (the steps across rows never wrote row 0), then the same `+ carry`, the carry of their
+      // component picked by row; the carries out of the last trip are not needed.  One product, four DPP adds, one add and
+      // one store per lane and scan.
+      const int t = (int)lane & 15, k = (int)lane >> 4, d = last + t;
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int c = 4 * h + k;
+        const bool on = t < rem && c < 6;
+        vreal x = vreal(0.);
+        if (on) x = s[LO(cdof) + 6 * d + c] * s[vec + d];
+        VNL_OPAQUE(x);  // (rounded, as above)
+        x = vnl_row_scan(x);
+        const vreal cr = h == 0 ? (k == 0 ? carry.a.x : k == 1 ? carry.a.y : k == 2 ? carry.a.z : carry.l.x)
+                                : (k == 0 ? carry.l.y : carry.l.z);
+        x = x + cr;
+        if (on) s[Q + 6 * (d + 1) + c] = x;
+      }
+    }
+#endif
     VNL_SYNC();
   }
   // sum over the (at most 4) runs of consecutive dofs on a body's path: Q[end] - Q[begin] each; run(k) = begin | end << 8
@@ -2197,8 +2371,9 @@ struct EnvWaveT {
             w = S6{cross(rel, Fw), Fw};
           }
         }
-        VNL_SCAN_ADD(w.a.x, run.a.x), VNL_SCAN_ADD(w.a.y, run.a.y), VNL_SCAN_ADD(w.a.z, run.a.z);
-        VNL_SCAN_ADD(w.l.x, run.l.x), VNL_SCAN_ADD(w.l.y, run.l.y), VNL_SCAN_ADD(w.l.z, run.l.z);
+        // (no carry: where a row outside a row_bcast step's mask held -0.0 it now keeps it, the former form left +0.0 -- a
+        // difference of two such entries is the same number either way, see vnl_rows_join)
+        VNL_SCAN6(w, run);
         if (k < MI(ncon)) st6(Wc + 6 * (k + 1), w);
         if (k == 0) st6(Wc, S6{v3(0, 0, 0), v3(0, 0, 0)});
       }
@@ -2279,8 +2454,10 @@ struct EnvWaveT {
     // (few: every row sits in one of the first 16 lanes -- the usual case, a dozen live rows: the short reduction)
     if (few) {
       for (int i = 0; i < N; i++) q0[i] = vnl_wave_sum16(q0[i]), q1[i] = vnl_wave_sum16(q1[i]), q2[i] = vnl_wave_sum16(q2[i]);
+    } else if constexpr (N == 3) {  // (the nine sums share the row-crossing stage)
+      VNL_WAVE_SUMS(q0[0], q1[0], q2[0], q0[1], q1[1], q2[1], q0[2], q1[2], q2[2]);
     } else {
-      for (int i = 0; i < N; i++) q0[i] = vnl_wave_sum(q0[i]), q1[i] = vnl_wave_sum(q1[i]), q2[i] = vnl_wave_sum(q2[i]);
+      for (int i = 0; i < N; i++) VNL_WAVE_SUMS(q0[i], q1[i], q2[i]);
     }
     for (int i = 0; i < N; i++) {
       vreal t0 = qg0 + q0[i], t1 = qg1 + q1[i], t2 = qg2 + q2[i];
@@ -2515,8 +2692,12 @@ struct EnvWaveT {
         qg2c += sd * md;
       }
     }
-    ss = vnl_wave_sum(ss), gp = vnl_wave_sum(gp);
-    if (qg_carried) qg1c = vnl_wave_sum(qg1c), qg2c = vreal(0.5) * vnl_wave_sum(qg2c);
+    if (qg_carried) {
+      VNL_WAVE_SUMS(ss, gp, qg1c, qg2c);
+      qg2c = vreal(0.5) * qg2c;
+    } else {
+      VNL_WAVE_SUMS(ss, gp);
+    }
     VNL_SYNC();
     if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
     VNL_PROF(15);
@@ -2539,7 +2720,8 @@ struct EnvWaveT {
           qg1 += sd * s[LO(Ma) + d] - sd * s[LO(smooth) + d];
           qg2 += sd * s[LO(mv) + d];
         }
-        qg1 = vnl_wave_sum(qg1), qg2 = vreal(0.5) * vnl_wave_sum(qg2);
+        VNL_WAVE_SUMS(qg1, qg2);
+        qg2 = vreal(0.5) * qg2;
       }
       VNL_PROF(18);
       int* tr = (trace && it < VNL_TRACE_ITERS) ? trace + 8 + VNL_TRACE_REC * it : nullptr;
@@ -2608,7 +2790,7 @@ struct EnvWaveT {
         s[LO(grad) + d] = gn, s[LO(tmp) + d] = gn;
         gg += gn * gn;
       }
-      d1 = vnl_wave_sum(d1), gg = vnl_wave_sum(gg);
+      VNL_WAVE_SUMS(d1, gg);
       VNL_SYNC();
       VNL_PROF(23);
       if (newton) fresh().newton_solve(LO(tmp));
@@ -2646,8 +2828,12 @@ struct EnvWaveT {
         }
       }
 #endif
-      ss = vnl_wave_sum(ss);
-      if (qg_carried) qg1c = vnl_wave_sum(qg1c), qg2c = vreal(0.5) * vnl_wave_sum(qg2c);
+      if (qg_carried) {
+        VNL_WAVE_SUMS(ss, qg1c, qg2c);
+        qg2c = vreal(0.5) * qg2c;
+      } else {
+        ss = vnl_wave_sum(ss);
+      }
       VNL_SYNC();
       if (newton) fresh().newton_mass_mul(LO(search), LO(mv));
       VNL_PROF(25);
@@ -2910,7 +3096,7 @@ struct EnvWaveT {
       cy += fabs(vreal(cb[3 * k + 1]) - xpos[3 * bd + 1]);
       cz += fabs(vreal(cb[3 * k + 2]) - xpos[3 * bd + 2]);
     }
-    ej = vnl_wave_sum(ej), cx = vnl_wave_sum(cx), cy = vnl_wave_sum(cy), cz = vnl_wave_sum(cz);
+    VNL_WAVE_SUMS(ej, cx, cy, cz);
     vreal eb = fmax(cx, fmax(cy, cz));
     if (ev.flags & VNL_ENV_TERM_MEAN) {  // humanoid.py:256-260: jp.mean(jp.abs(.)) over the (nb, 3) and (nj,) differences
       eb = (cx + cy + cz) / vreal(3 * ev.nb);
