@@ -4,6 +4,8 @@ import copy
 
 import numpy as np
 
+import helpers as H
+
 FIELDS = ("cg_friction", "act_gain", "dof_damping", "dof_armature")
 # the issue's spread: friction x U[0.4, 1.6], gain x U[0.7, 1.3], damping and armature x U[0.5, 2]
 SPREAD = {"cg_friction": (0.4, 1.6), "act_gain": (0.7, 1.3), "dof_damping": (0.5, 2.0), "dof_armature": (0.5, 2.0)}
@@ -44,7 +46,27 @@ def row(dom: dict, i: int) -> dict:
     return {k: v[i:i + 1] for k, v in dom.items()}
 
 
-# the ant (generic kernel) as tests/test_ant_env.py builds it: CG 6 / 6, a seeded gait around the init pose as its clip
+OUT_KEYS = ("qpos", "qvel", "act", "qacc_warmstart", "xpos", "qfrc_actuator")
+
+
+def inputs(B, nq=74, nu=30, seed=0):
+    rng = np.random.default_rng(seed)
+    sf = rng.integers(0, 235, B).astype(np.int32)
+    noise = 1e-3 * rng.standard_normal((B, nq))
+    acts = np.clip(0.3 * rng.standard_normal((3, B, nu)), -1, 1)
+    return sf, noise, acts
+
+
+def row_err(st, ost, i):
+    """Env i of a batch against the oracle state of a one-env batch: scaled errors per output."""
+    ps = st.pipeline_state
+    out = {k: H.scaled_err(getattr(ps, k).reshape(st.obs.shape[0], -1)[i:i + 1].numpy(), ost[k]) for k in OUT_KEYS}
+    out["obs"] = H.scaled_err(st.obs[i:i + 1].numpy(), ost["obs"])
+    out["traj"] = H.scaled_err(st.info["traj"][i:i + 1].numpy(), ost["traj"])
+    return out
+
+
+# the ant (generic kernel) as tests/model_cases.py builds it: CG 6 / 6, a seeded gait around the init pose as its clip
 ANT_PARAMS = dict(solver="cg", iterations=6, ls_iterations=6)
 
 

@@ -65,22 +65,30 @@ def env_kwargs() -> dict:
     return kw
 
 
-def build_hostsim(real: str = "float") -> str:
-    """g++ build of csrc/vnl_lib.hip against tests/hostsim/stub (kernel launch = serial loop)."""
+# the regression builds of csrc/build.py VARIANTS that have a host counterpart: file suffix -> define
+HOSTSIM_VARIANTS = {"tail": "VNL_SOLVER_TAIL", "plain": "VNL_SOLVER_PLAIN", "vmemplain": "VNL_VMEM_PLAIN",
+                    "ldsplain": "VNL_LDS_PLAIN"}
+
+
+def build_hostsim(real: str = "float", variant: str | None = None) -> str:
+    """g++ build of csrc/vnl_lib.hip against tests/hostsim/stub (kernel launch = serial loop); `variant`: with the define of
+    that regression build."""
     src = os.path.join(ROOT, "vnl-brax-imitation_amd", "csrc")
-    out = os.path.join(ROOT, "tests", "hostsim", "_build", f"libvnl_hostsim_{real}.so")
+    out = os.path.join(ROOT, "tests", "hostsim", "_build", f"libvnl_hostsim_{real}{'_' + variant if variant else ''}.so")
     deps = [os.path.join(src, f) for f in os.listdir(src) if f.endswith((".h", ".hip"))]
     deps += [os.path.join(ROOT, "include", "vnl.h"), os.path.join(ROOT, "tests", "hostsim", "stub", "hip", "hip_runtime.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", f"-DVNL_REAL={real}", "-I" + os.path.join(ROOT, "tests", "hostsim", "stub"),
-                               "-x", "c++", os.path.join(src, "vnl_lib.hip"), "-o", out])
+        defs = [f"-DVNL_REAL={real}"] + (["-D" + HOSTSIM_VARIANTS[variant]] if variant else [])
+        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17"] + defs +
+                              ["-I" + os.path.join(ROOT, "tests", "hostsim", "stub"), "-x", "c++",
+                               os.path.join(src, "vnl_lib.hip"), "-o", out])
     return out
 
 
 @functools.lru_cache(maxsize=None)
-def hostsim_library(real: str = "float") -> C.CDLL:
-    return _lib.load_library(build_hostsim(real), env_only=True)
+def hostsim_library(real: str = "float", variant: str | None = None) -> C.CDLL:
+    return _lib.load_library(build_hostsim(real, variant), env_only=True)
 
 
 import contextlib  # noqa: E402
@@ -119,6 +127,25 @@ def hostsim_env(num_envs: int, real: str = "float", **over):
     clip = kw.pop("reference_clip", None) or reference_clip()
     with hostsim_backend(real):
         return RodentTracking(clip, num_envs=num_envs, device="cpu", **kw)
+
+
+def unroll_setup(B, reset_info, episode_length, make_env, device):
+    """make_env(B) under the Episode and AutoReset wrappers, and the acting policy of a small intention network on it."""
+    import torch
+
+    from vnl_brax_imitation_amd.envs.wrappers import AutoResetWrapper, EpisodeWrapper
+    from vnl_brax_imitation_amd.ppo_imitation import ppo_networks, running_statistics
+
+    base = make_env(B)
+    env = AutoResetWrapper(EpisodeWrapper(base, episode_length=episode_length, action_repeat=1),
+                           reset_info_on_autoreset=reset_info)
+    nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
+                                                    preprocess_observations_fn=running_statistics.normalize,
+                                                    intention_latent_size=16, encoder_layer_sizes=(32,),
+                                                    decoder_layer_sizes=(32,))
+    flat = nets.policy_network.init(torch.Generator().manual_seed(0)).to(device)
+    norm = running_statistics.init_state(base.observation_size, device=device)
+    return env, ppo_networks.make_inference_fn(nets)((norm, flat))
 
 
 def make_oracle(env, precision="f64"):

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 import fresh_reset_cases as F
-import helpers as H
+import model_cases as M
 from vnl_brax_imitation_amd import _lib
 from vnl_brax_imitation_amd.ppo_imitation import philox
 
@@ -18,18 +18,8 @@ UPDATE_NCELLS = (1, 2, 63, 64, 65, 705, 4096, 4097, 15040, 32768)
 
 
 def ant_env(num_envs, device="cpu"):
-    """AntTracking on three copies of tests/test_ant_env.py's clip"""
-    import contextlib
-
-    import test_ant_env as A
-    from vnl_brax_imitation_amd import envs
-    from vnl_brax_imitation_amd.model import mjcf
-
-    m = mjcf.CompiledModel.load(A.ANT_NPZ)
-    c = A._clip(m)
-    with (H.hostsim_backend("float") if device == "cpu" else contextlib.nullcontext()):
-        return envs.get_environment("ant", params=A.PARAMS, clip_length=60, episode_length=20,
-                                    reference_clip=type(c).stack([c, c, c]), model=m, num_envs=num_envs, device=device)
+    """AntTracking on three copies of model_cases.ant_clip"""
+    return M.ant_env(num_envs, "float", device, clips=3)
 
 
 def as_words(values) -> torch.Tensor:

@@ -3,42 +3,14 @@
 CPU tier: the float64 host build of the kernels against the dense oracle, and the statements of ant.py that differ from
 the rodent env, checked directly.  GPU tier: one control step through the C-ABI, following the solver decisions, and the
 glue on the product's own state.  The reference's ant clip is not shipped: the clip is a seeded gait around the init pose."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import helpers as H
 import parity as P
-from vnl_brax_imitation_amd.model import mjcf
-from vnl_brax_imitation_amd.preprocessing import mjx_preprocess as pp
-
-ANT_NPZ = os.path.join(H.ROOT, "vnl-brax-imitation_amd", "data", "ant.npz")
-PARAMS = dict(solver="cg", iterations=6, ls_iterations=6)
-
-
-def _clip(m, T=60):
-    t = np.arange(T)[:, None] * 0.02
-    q = np.zeros((T, 15))
-    q[:, 2], q[:, 3] = 0.55, 1.0
-    q[:, 0] = 0.2 * t[:, 0]
-    q[:, 7:] = np.array([0.0, 1.0, 0.0, -1.0, 0.0, -1.0, 0.0, 1.0]) + 0.15 * np.sin(2 * np.pi * 1.5 * t + np.arange(8))
-    return pp.process_qpos(m, q, max_qvel=20.0, dt=0.02)
-
-
-NEWTON = dict(solver="newton", iterations=1, ls_iterations=4)  # reference configs/env_config.yaml:16-21
-
-
-def _env(B, real="float", device="cpu", params=None, **kw):
-    from vnl_brax_imitation_amd import envs
-
-    m = mjcf.CompiledModel.load(ANT_NPZ)
-    import contextlib
-
-    with (H.hostsim_backend(real) if device == "cpu" else contextlib.nullcontext()):
-        return envs.get_environment("ant", params=params or PARAMS, clip_length=60, episode_length=20, reference_clip=_clip(m), model=m,
-                                    num_envs=B, device=device, **kw)
+from model_cases import NEWTON
+from model_cases import ant_env as _env
 
 
 def _oracle(env, precision="f64"):

@@ -13,30 +13,13 @@ import torch
 
 import domain_cases as D
 import helpers as H
+from domain_cases import inputs as _inputs
+from domain_cases import row_err as _row_err
 from vnl_brax_imitation_amd import _lib
 from vnl_brax_imitation_amd.envs import wrappers as W
 from vnl_brax_imitation_amd.model import mjcf
 from vnl_brax_imitation_amd.ppo_imitation import acting
 from vnl_brax_imitation_amd.ppo_imitation import train as ppo
-
-OUT_KEYS = ("qpos", "qvel", "act", "qacc_warmstart", "xpos", "qfrc_actuator")
-
-
-def _inputs(B, nq=74, nu=30, seed=0):
-    rng = np.random.default_rng(seed)
-    sf = rng.integers(0, 235, B).astype(np.int32)
-    noise = 1e-3 * rng.standard_normal((B, nq))
-    acts = np.clip(0.3 * rng.standard_normal((3, B, nu)), -1, 1)
-    return sf, noise, acts
-
-
-def _row_err(st, ost, i):
-    ps = st.pipeline_state
-    out = {k: H.scaled_err(getattr(ps, k).reshape(st.obs.shape[0], -1)[i:i + 1].numpy(), ost[k]) for k in OUT_KEYS}
-    out["obs"] = H.scaled_err(st.obs[i:i + 1].numpy(), ost["obs"])
-    out["traj"] = H.scaled_err(st.info["traj"][i:i + 1].numpy(), ost["traj"])
-    return out
-
 
 def _outputs(st) -> dict:
     ps = st.pipeline_state

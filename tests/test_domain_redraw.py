@@ -90,8 +90,6 @@ def test_unfinished_envs_keep_their_first_domain(model):
 def test_float64_build_follows_the_oracle_of_each_envs_drawn_model():
     """Case 8: 4 rodent envs after a redraw, each against the float64 oracle of ITS model over a reset and one control step
     (the bounds of tests/test_domain_randomization.py: the kernels read what was drawn)."""
-    from test_domain_randomization import _inputs, _row_err
-
     n = 4
     base = H.hostsim_env(n, "double")
     rg = R.ranges_for(base.sys, 8)
@@ -99,20 +97,20 @@ def test_float64_build_follows_the_oracle_of_each_envs_drawn_model():
     R.redraw(env)
     dom = {k: v.numpy() for k, v in R.drawn(env, rg, shared=("cg_friction",)).items()}
     assert np.array_equal(env.domain_table("dom_damp").numpy(), dom["dof_damping"])
-    sf, noise, acts = _inputs(n, seed=3)
+    sf, noise, acts = D.inputs(n, seed=3)
     st = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
     osts = []
     for i in range(n):
         one = H.hostsim_env(1, "double", model=D.model_with(base.sys, dom, i))
         o = H.make_oracle(one, "f64")
         ost = o.env_reset(sf[i:i + 1], noise[i:i + 1])
-        e = _row_err(st, ost, i)
+        e = D.row_err(st, ost, i)
         assert max(e.values()) < 1e-11, (i, e)
         osts.append((o, ost))
     st = env.step(st, torch.from_numpy(acts[0]))
     for i, (o, ost) in enumerate(osts):
         o.env_step(ost, acts[0][i:i + 1])
-        e = _row_err(st, ost, i)
+        e = D.row_err(st, ost, i)
         assert max(e.values()) < 1e-8, (i, e)
         assert np.array_equal(st.done[i:i + 1].numpy(), ost["done"])
 

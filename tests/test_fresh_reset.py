@@ -8,6 +8,7 @@ import torch
 
 import fresh_reset_cases as F
 import helpers as H
+from model_cases import humanoid_env
 from vnl_brax_imitation_amd import _lib
 from vnl_brax_imitation_amd.envs.wrappers import AutoResetWrapper, EpisodeWrapper, wrap
 from vnl_brax_imitation_amd.ppo_imitation import acting, philox, ppo_networks, running_statistics
@@ -164,8 +165,6 @@ def test_fresh_reset_is_the_existing_reset_in_the_double_build():
 def test_humanoid_and_ant_draw_from_the_range_of_their_own_reset():
     """The start frames of a fresh reset are those of the env's OWN reset: the humanoid's U[0, clip_length - episode_length -
     ref_traj_length) (its sub-clip term is off), the ant's frame 0; neither adds reset noise."""
-    from test_humanoid import _env as humanoid_env
-
     env = humanoid_env(8)
     assert env._start_hi() == 60 - 20 - 5
     st = env.reset(start_frame=torch.zeros(8, dtype=torch.int32))

@@ -4,21 +4,8 @@ import pytest
 import torch
 
 import helpers as H
-from vnl_brax_imitation_amd.envs.wrappers import AutoResetWrapper, EpisodeWrapper
-from vnl_brax_imitation_amd.ppo_imitation import acting, ppo_networks, running_statistics
-
-
-def _setup(B, reset_info, episode_length, make_env, device):
-    base = make_env(B)
-    env = AutoResetWrapper(EpisodeWrapper(base, episode_length=episode_length, action_repeat=1),
-                           reset_info_on_autoreset=reset_info)
-    nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
-                                                    preprocess_observations_fn=running_statistics.normalize,
-                                                    intention_latent_size=16, encoder_layer_sizes=(32,),
-                                                    decoder_layer_sizes=(32,))
-    flat = nets.policy_network.init(torch.Generator().manual_seed(0)).to(device)
-    norm = running_statistics.init_state(base.observation_size, device=device)
-    return env, ppo_networks.make_inference_fn(nets)((norm, flat))
+from helpers import unroll_setup as _setup
+from vnl_brax_imitation_amd.ppo_imitation import acting
 
 
 def _compare(make_env, device, reset_info, B=6, T=7):

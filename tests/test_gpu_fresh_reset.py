@@ -9,6 +9,7 @@ import body_domain_cases as BD
 import domain_cases as D
 import fresh_reset_cases as F
 import helpers as H
+from model_cases import ant_as_rodent_env as _ant_env
 from vnl_brax_imitation_amd.envs.rodent import RodentTracking
 from vnl_brax_imitation_amd.envs.wrappers import AutoResetWrapper, EpisodeWrapper
 from vnl_brax_imitation_amd.ppo_imitation import acting, ppo_networks, running_statistics
@@ -37,8 +38,6 @@ def test_specialised_rodent_kernel_256_envs():
 
 
 def test_generic_kernel_64_envs():
-    from test_generic_model import _ant_env
-
     env = _ant_env(64, "float", device="cuda:0")
     assert env.dims.kernel_specialised == 0
     F.check_items_1_to_3(env, *_masks(64))
@@ -51,8 +50,6 @@ def test_randomised_env_keeps_its_tables_64_envs(model):
     if model == "rodent":
         base = _rodent(64)
     else:
-        from test_generic_model import _ant_env
-
         base = _ant_env(64, "float", device="cuda:0")
     env = base.with_domain(D.random_domain(base.sys, 64, 21)).with_body_domain(BD.random_body_domain(base.sys, 64, 22))
     tables = {k: env.domain_table(k) for k in DOM_TABLES}

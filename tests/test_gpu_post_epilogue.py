@@ -12,19 +12,13 @@ import torch
 import domain_cases as D
 import helpers as H
 import post_epilogue_cases as PE
+from variant_cases import variant as _variant
 from vnl_brax_imitation_amd import _lib
 from vnl_brax_imitation_amd.envs.rodent import RodentTracking
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 B = 67
-
-
-@functools.lru_cache(maxsize=None)
-def _variant(name):
-    from vnl_brax_imitation_amd.csrc import build as hip_build
-
-    return _lib.load_library(hip_build.build(variant=name))
 
 
 def _rodent(lib=None, domain=False, n=B):

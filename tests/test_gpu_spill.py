@@ -11,19 +11,13 @@ import torch
 
 import helpers as H
 import parity as P
+from variant_cases import rodent as _env
+from variant_cases import variant
 
 pytestmark = pytest.mark.gpu
 
 
-def _env(B, lib=None):
-    from vnl_brax_imitation_amd.envs.rodent import RodentTracking
-
-    with H.backend(lib):
-        return RodentTracking(H.reference_clip(), num_envs=B, device="cuda:0", **H.env_kwargs())
-
-
 def test_spilling_build_matches_oracle_and_product_build():
-    from vnl_brax_imitation_amd import _lib
     from vnl_brax_imitation_amd.csrc import build as hip_build
 
     path = hip_build.build(variant="spill")
@@ -35,14 +29,14 @@ def test_spilling_build_matches_oracle_and_product_build():
     sf = rng.integers(0, 235, B).astype(np.int32)
     noise = (1e-3 * rng.standard_normal((B, 74))).astype(np.float32)
     acts = np.clip(0.3 * rng.standard_normal((3, B, 30)), -1, 1).astype(np.float32)
-    spill = _env(B, _lib.load_library(path))
+    spill = _env(B, variant("spill"))
     o64, o32 = H.make_oracle(spill, "f64"), H.make_oracle(spill, "f32")
     st, err, dev, rep, ost = P.control_step_follow(spill, o64, o32, sf, noise, acts[0])
     print("\n[spill build, control step] " + ", ".join(f"{k} max {v.max():.2e}" for k, v in err.items()))
     P.check_control_step(err, dev, rep)
     # three steps on both builds: same instructions modulo spill code, so the outputs should agree bit for bit; a
     # difference beyond float32 rounding of one step would be a spill-dependent result
-    prod = _env(B)
+    prod = _env(B, None)
     outs = []
     for env in (spill, prod):
         s = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
@@ -63,21 +57,14 @@ def test_blocked_products_agree_with_the_lane_per_row_products():
     builds the same sources with one lane per row / column: the same sums in another order.  One substep from identical
     states may differ by the rounding of those sums and what six CG iterations make of it -- nothing more: the median env
     within 1e-6 of scale on the velocities, and no more envs beyond 1e-5 than the product has against the float64 oracle."""
-    from vnl_brax_imitation_amd import _lib
-    from vnl_brax_imitation_amd.csrc import build as hip_build
-    from vnl_brax_imitation_amd.envs.rodent import RodentTracking
-
-    path = hip_build.build(variant="noblk")
     B = 1024
     rng = np.random.default_rng(33)
     sf = rng.integers(0, 235, B).astype(np.int32)
     noise = (1e-3 * rng.standard_normal((B, 74))).astype(np.float32)
     act = np.clip(0.3 * rng.standard_normal((B, 30)), -1, 1).astype(np.float32)
-    kw = dict(H.env_kwargs(), n_frames=1)
     outs = []
-    for lib in (_lib.load_library(path), None):
-        with H.backend(lib):
-            env = RodentTracking(H.reference_clip(), num_envs=B, device="cuda:0", **kw)
+    for lib in (variant("noblk"), None):
+        env = _env(B, lib, n_frames=1)
         s = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
         ps0 = {k: getattr(s.pipeline_state, k).cpu().numpy().copy() for k in ("qpos", "qvel", "qacc_warmstart")}
         s = env.step(s, torch.from_numpy(act))
@@ -97,20 +84,16 @@ def test_specialised_kernels_equal_the_generic_kernels_bit_for_bit():
     loop bounds fold, offsets become instruction immediates); csrc/build.py --nospec builds the same sources with the
     specialisation switched off, so that the generic kernels (every dimension read from the constant block: what any other
     model runs) take the rodent too.  Same operations on the same operands in the same order: bit-identical outputs."""
-    from vnl_brax_imitation_amd import _lib
-    from vnl_brax_imitation_amd.csrc import build as hip_build
-
-    path = hip_build.build(variant="nospec")
     B = 512
     # the product runs the specialised kernels on the rodent (a mismatch of the compile-time constants would fall back to the
     # generic ones silently), the regression build the generic ones
-    assert int(_env(4).dims.kernel_specialised) == 1 and int(_env(4, _lib.load_library(path)).dims.kernel_specialised) == 0
+    assert int(_env(4, None).dims.kernel_specialised) == 1 and int(_env(4, variant("nospec")).dims.kernel_specialised) == 0
     rng = np.random.default_rng(44)
     sf = rng.integers(0, 235, B).astype(np.int32)
     noise = (1e-3 * rng.standard_normal((B, 74))).astype(np.float32)
     acts = np.clip(0.3 * rng.standard_normal((3, B, 30)), -1, 1).astype(np.float32)
     outs = []
-    for env in (_env(B, _lib.load_library(path)), _env(B)):
+    for env in (_env(B, variant("nospec")), _env(B, None)):
         s = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
         for a in acts:
             s = env.step(s, torch.from_numpy(a))

@@ -2,127 +2,36 @@
 and deferred 1/D2 store, euler()'s batched reload of the second inverse factor, forward()'s warm start, the table reads of a
 trip requested together): the product library against the regression build with the former accesses
 (csrc/build.py --vmemplain).  The same values by another route: every output bit for bit."""
-import functools
-
-import numpy as np
 import pytest
-import torch
 
-import domain_cases as D
-import helpers as H
-import test_gpu_solver_staging as S
-import test_humanoid as Hu
-import test_solver_tail as T
-from vnl_brax_imitation_amd import _lib
-from vnl_brax_imitation_amd.envs import wrappers as W
-from vnl_brax_imitation_amd.envs.rodent import RodentTracking
-from vnl_brax_imitation_amd.ppo_imitation import acting, ppo_networks, running_statistics
+import variant_cases as V
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 STEPS = 2
 
 
-@functools.lru_cache(maxsize=None)
-def _variant(name):
-    from vnl_brax_imitation_amd.csrc import build as hip_build
-
-    return _lib.load_library(hip_build.build(variant=name))
-
-
-def _rodent(n, lib, domain=None):
-    with H.backend(lib):
-        base = RodentTracking(H.reference_clip(), num_envs=n, device=DEV, **H.env_kwargs())
-        return base if domain is None else base.with_domain(domain(base.sys, n))
-
-
-def _rollout(env, n):
-    """reset + two control steps on the inputs of tests/test_gpu_solver_staging.py (several envs with contacts)."""
-    sf, noise, acts = S._inputs(n)
-    st = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
-    snaps = [T._outputs(st)]
-    for a in acts[:STEPS]:
-        st = env.step(st, torch.from_numpy(a))
-        snaps.append(T._outputs(st))
-    return snaps
-
-
-def _same(a_snaps, b_snaps, tag):
-    assert len(a_snaps) == len(b_snaps) == STEPS + 1
-    for t, (a, b) in enumerate(zip(a_snaps, b_snaps)):
-        assert a.keys() == b.keys()
-        for k in a:
-            assert torch.equal(a[k], b[k]), (tag, t, k)
-    assert not torch.equal(a_snaps[-1]["ps.qpos"], a_snaps[0]["ps.qpos"])
-    assert all(torch.isfinite(v).all() for k, v in a_snaps[-1].items() if v.is_floating_point()), tag
-
-
-def _friction(sys, n):
-    return {"cg_friction": D.random_domain(sys, n, 21)["cg_friction"]}
-
-
-def _damping_armature(sys, n):
-    dom = D.random_domain(sys, n, 22)
-    return {"dof_damping": dom["dof_damping"], "dof_armature": dom["dof_armature"]}  # (damping feeds D2, armature both pivots)
-
-
-@pytest.mark.parametrize("domain", [_friction, _damping_armature], ids=["friction", "damping_armature"])
+@pytest.mark.parametrize("domain", [V.friction, V.damping_armature], ids=["friction", "damping_armature"])
 def test_vector_memory_schedule_changes_no_bit_on_the_rodent(domain):
     """64 envs, the randomised instantiation of the specialised kernels."""
     n = 64
-    new, old = _rodent(n, None, domain), _rodent(n, _variant("vmemplain"), domain)
+    new, old = V.rodent(n, None, domain), V.rodent(n, V.variant("vmemplain"), domain)
     assert int(new.dims.kernel_specialised) == 1 and int(old.dims.kernel_specialised) == 1
-    _same(_rollout(new, n), _rollout(old, n), domain.__name__)
+    V.same(V.rollout(new, n, STEPS), V.rollout(old, n, STEPS), domain.__name__, STEPS)
 
 
 def test_generic_kernels_equal_the_specialised_ones_on_the_rodent():
     """The generic kernels keep a four-word window of the schedule and refill it; the specialised ones hold the row."""
     n = 64
-    new, gen = _rodent(n, None), _rodent(n, _variant("nospec"))
+    new, gen = V.rodent(n, None), V.rodent(n, V.variant("nospec"))
     assert int(new.dims.kernel_specialised) == 1 and int(gen.dims.kernel_specialised) == 0
-    _same(_rollout(new, n), _rollout(gen, n), "nospec")
+    V.same(V.rollout(new, n, STEPS), V.rollout(gen, n, STEPS), "nospec", STEPS)
 
 
 def test_vector_memory_schedule_changes_no_bit_on_the_humanoid():
     n = 32
-    outs = []
-    for lib in (None, _variant("vmemplain")):
-        with H.backend(lib):
-            env = Hu._env(n, device=DEV)
-        rng = np.random.default_rng(3)
-        st = env.reset(5)
-        snaps = [T._outputs(st)]
-        for _ in range(STEPS):
-            st = env.step(st, torch.from_numpy(np.clip(0.3 * rng.standard_normal((n, 21)), -1, 1).astype(np.float32)))
-            snaps.append(T._outputs(st))
-        outs.append(snaps)
-    _same(outs[0], outs[1], "humanoid")
+    V.same(V.humanoid_rollout(None, n, STEPS), V.humanoid_rollout(V.variant("vmemplain"), n, STEPS), "humanoid", STEPS)
 
 
 def test_graphed_unroll_replay_equals_the_eager_fused_unroll():
     """One 20-step replay of a captured unroll, 64 envs: the step kernel inside a graph, resets included."""
-    B, steps = 64, 20
-    out = []
-    for graphed in (False, True):
-        base = _rodent(B, None)
-        env = W.AutoResetWrapper(W.EpisodeWrapper(base, episode_length=8, action_repeat=1))
-        nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
-                                                        preprocess_observations_fn=running_statistics.normalize,
-                                                        intention_latent_size=16, encoder_layer_sizes=(32,),
-                                                        decoder_layer_sizes=(32,))
-        flat = nets.policy_network.init(torch.Generator().manual_seed(0)).to(DEV)
-        policy = ppo_networks.make_inference_fn(nets)((running_statistics.init_state(base.observation_size, device=DEV), flat))
-        torch.manual_seed(123)
-        state = env.reset(torch.Generator().manual_seed(5))
-        key = torch.Generator(device=DEV).manual_seed(11)
-        if graphed:
-            state, data = acting.GraphedUnroll(env, state, policy, key, steps, extra_fields=("truncation",))()
-        else:
-            state, data = acting.generate_unroll(env, state, policy, key, steps, extra_fields=("truncation",), fused=True)
-        out.append((state, [x.clone() for x in acting._leaves(data)]))
-    (s0, d0), (s1, d1) = out
-    assert len(d0) == len(d1)
-    for a, b in zip(d0, d1):
-        assert torch.equal(a, b)
-    for n in s0.pipeline_state._FIELDS:
-        assert torch.equal(s0.pipeline_state.raw(n), s1.pipeline_state.raw(n)), n
+    V.same_unroll(V.small_unroll(None, 64, graphed=False), V.small_unroll(None, 64, graphed=True))

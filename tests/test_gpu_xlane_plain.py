@@ -6,26 +6,18 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
-import helpers as H
-import test_gpu_sgpr_plain as G
-import test_gpu_solver_staging as S
-import test_humanoid as Hu
-import test_solver_tail as T
-from vnl_brax_imitation_amd.envs import wrappers as W
-from vnl_brax_imitation_amd.ppo_imitation import acting, ppo_networks, running_statistics
+import variant_cases as V
 
 pytestmark = pytest.mark.gpu
-DEV = G.DEV
-STEPS = G.STEPS
-N = G.N  # 128 envs: the rodent's 73 dofs take both trips of every carried scan, the second one in the tail form
+STEPS = 3
+N = 128  # 128 envs: the rodent's 73 dofs take both trips of every carried scan, the second one in the tail form
 TRACE_ROWS = 8 + 64 * 8  # csrc/vnl_types.h VNL_TRACE_ROWS: then 16 ints, bit r set = constraint row r exists (D != 0)
 FEW = 16  # the line search's short path: at most this many existing rows, one per lane of a DPP row
 
 
 def _old():
-    return G._variant("xlaneplain")
+    return V.variant("xlaneplain")
 
 
 def _existing_rows(env):
@@ -36,16 +28,13 @@ def _existing_rows(env):
 
 @functools.lru_cache(maxsize=None)
 def _rows_of_the_rodent_inputs():
-    """Existing rows per env and solver call over the rollout of G._rollout, from a debug run of the regression build."""
-    env = G._rodent(N, _old())
+    """Existing rows per env and solver call over the rollout the tests below compare, from a debug run of the regression
+    build (of the reset's trace, the one solver call it makes)."""
+    env = V.rodent(N, _old())
     env.debug(True)
-    sf, noise, acts = S._inputs(N)
-    st = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
-    rows = [_existing_rows(env)[:, :1]]
-    for a in acts[:STEPS]:
-        st = env.step(st, torch.from_numpy(a))
-        rows.append(_existing_rows(env))
-    return np.concatenate(rows, axis=1)
+    rows = []
+    V.rollout(env, N, STEPS, each=lambda e: rows.append(_existing_rows(e)))
+    return np.concatenate([rows[0][:, :1]] + rows[1:], axis=1)
 
 
 def test_the_inputs_take_both_line_search_paths():
@@ -57,68 +46,30 @@ def test_the_inputs_take_both_line_search_paths():
     assert ((rows <= FEW) & (rows > 0)).any(1).sum() >= 1 and (rows > FEW).any(1).sum() >= 1
 
 
-@pytest.mark.parametrize("domain", [None, G._damping_armature], ids=["plain", "with_domain"])
+@pytest.mark.parametrize("domain", [None, V.damping_armature], ids=["plain", "with_domain"])
 def test_cross_lane_forms_change_no_bit_on_the_rodent(domain):
     """128 envs, the specialised kernels (CG 6 / 6) and their randomised instantiation (VnlSpecDom): both trips of every
     carried scan, the tail form as a compile-time fact."""
-    new, old = G._rodent(N, None, domain), G._rodent(N, _old(), domain)
+    new, old = V.rodent(N, None, domain), V.rodent(N, _old(), domain)
     assert int(new.dims.kernel_specialised) == 1 and int(old.dims.kernel_specialised) == 1
-    G._same(G._rollout(new, N), G._rollout(old, N), "plain" if domain is None else "with_domain")
+    V.same(V.rollout(new, N, STEPS), V.rollout(old, N, STEPS), "plain" if domain is None else "with_domain", STEPS)
 
 
 def test_generic_kernels_with_the_new_forms_equal_the_former_specialised_ones():
     """The shipped `nospec` library has the new forms (only -DVNL_XLANE_PLAIN switches them off): the generic kernels, where the
     tail form of dof_prefix is a wave-uniform branch at run time, against the former forms in the specialised kernel."""
-    gen, old = G._rodent(N, G._variant("nospec")), G._rodent(N, _old())
+    gen, old = V.rodent(N, V.variant("nospec")), V.rodent(N, _old())
     assert int(gen.dims.kernel_specialised) == 0 and int(old.dims.kernel_specialised) == 1
-    G._same(G._rollout(gen, N), G._rollout(old, N), "nospec")
+    V.same(V.rollout(gen, N, STEPS), V.rollout(old, N, STEPS), "nospec", STEPS)
 
 
 def test_cross_lane_forms_change_no_bit_on_the_humanoid():
     """64 envs, nv = 27: a single trip of every scan and no tail form -- the one-instruction row_bcast steps alone."""
     n = 64
-    outs = []
-    for lib in (None, _old()):
-        with H.backend(lib):
-            env = Hu._env(n, device=DEV)
-        rng = np.random.default_rng(3)
-        st = env.reset(5)
-        snaps = [T._outputs(st)]
-        for _ in range(STEPS):
-            st = env.step(st, torch.from_numpy(np.clip(0.3 * rng.standard_normal((n, 21)), -1, 1).astype(np.float32)))
-            snaps.append(T._outputs(st))
-        outs.append(snaps)
-    G._same(outs[0], outs[1], "humanoid")
+    V.same(V.humanoid_rollout(None, n, STEPS), V.humanoid_rollout(_old(), n, STEPS), "humanoid", STEPS)
 
 
 def test_graphed_unroll_equals_the_eager_unroll_of_the_regression_build():
     """One 20-step replay of a captured unroll with the product library, 128 envs (the step kernel inside a graph, resets
     included), against the eager fused unroll of the regression build."""
-    steps = 20
-    out = []
-    for lib, graphed in ((None, True), (_old(), False)):
-        base = G._rodent(N, lib)
-        with H.backend(lib):
-            env = W.AutoResetWrapper(W.EpisodeWrapper(base, episode_length=8, action_repeat=1))
-            nets = ppo_networks.make_intention_ppo_networks(base.traj_size, base.observation_size, base.action_size,
-                                                            preprocess_observations_fn=running_statistics.normalize,
-                                                            intention_latent_size=16, encoder_layer_sizes=(32,),
-                                                            decoder_layer_sizes=(32,))
-            flat = nets.policy_network.init(torch.Generator().manual_seed(0)).to(DEV)
-            policy = ppo_networks.make_inference_fn(nets)((running_statistics.init_state(base.observation_size, device=DEV), flat))
-            torch.manual_seed(123)
-            state = env.reset(torch.Generator().manual_seed(5))
-            key = torch.Generator(device=DEV).manual_seed(11)
-            if graphed:
-                state, data = acting.GraphedUnroll(env, state, policy, key, steps, extra_fields=("truncation",))()
-            else:
-                state, data = acting.generate_unroll(env, state, policy, key, steps, extra_fields=("truncation",), fused=True)
-        out.append((state, [x.clone() for x in acting._leaves(data)]))
-    (s0, d0), (s1, d1) = out
-    assert len(d0) == len(d1)
-    for a, b in zip(d0, d1):
-        assert torch.equal(a, b)
-    for n in s0.pipeline_state._FIELDS:
-        assert torch.equal(s0.pipeline_state.raw(n), s1.pipeline_state.raw(n)), n
-    q = s0.pipeline_state.raw("qpos")
-    assert torch.isfinite(q).all() and any(not torch.equal(x[0], x[-1]) for x in d0 if x.dim() > 1 and x.shape[0] == steps)
+    V.same_unroll(V.small_unroll(None, N, graphed=True), V.small_unroll(_old(), N, graphed=False), tail=True)

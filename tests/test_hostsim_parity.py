@@ -14,26 +14,8 @@ import pytest
 import torch
 
 import helpers as H
-
-KEYS = ("qpos", "qvel", "act", "qacc_warmstart", "xpos", "qfrc_actuator")
-
-
-def _inputs(B, seed=0):
-    rng = np.random.default_rng(seed)
-    sf = rng.integers(0, 235, B).astype(np.int32)
-    noise = 1e-3 * rng.standard_normal((B, 74))
-    acts = np.clip(0.3 * rng.standard_normal((3, B, 30)), -1, 1)
-    return sf, noise, acts
-
-
-def _cmp(st, ost, B):
-    out = {k: H.scaled_err(getattr(st.pipeline_state, k).reshape(B, -1).numpy(), ost[k]) for k in KEYS}
-    out["obs"] = H.scaled_err(st.obs.numpy(), ost["obs"])
-    out["traj"] = H.scaled_err(st.info["traj"].numpy(), ost["traj"])
-    out["reward"] = H.scaled_err(st.reward.numpy(), ost["reward"]) if np.abs(ost["reward"]).max() > 0 else 0.0
-    out["com"] = H.scaled_err(st.pipeline_state.subtree_com_root.numpy(), ost["com1"])
-    return out
-
+from hostsim_cases import parity_errors as _cmp
+from hostsim_cases import parity_inputs as _inputs
 
 def test_float64_build_is_algorithmically_identical_to_oracle():
     B = 16

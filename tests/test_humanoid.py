@@ -3,46 +3,18 @@
 The reference's clip (clips/humanoid_traj_stand.p) is not shipped; the clip here is the standing pose tiled, with a small
 seeded joint wobble so that joints / velocities are not all zero.  CPU tier: float64 host simulation of the kernels vs the
 dense oracle (algorithm equivalence), glue semantics.  GPU tier: parity at 1024 envs, following the solver decisions."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import helpers as H
 import parity as P
-from vnl_brax_imitation_amd.model import mjcf
-from vnl_brax_imitation_amd.preprocessing import mjx_preprocess as pp
+from model_cases import humanoid_env as _env
+from model_cases import humanoid_model as _model
 
 # helpers.model_digest of data/humanoid.npz, recorded when it was checked array for array against mjcf.compile_mjcf of the
 # reference's assets/humanoid.xml (scale_factor=None; the asset itself is not part of this repository)
 HUM_DIGEST = "a3154e00c5d9ab5e38d54e35e75baa2d3e54d97f7d64e42fe269a36cf15f86cb"
-HUM_NPZ = os.path.join(H.ROOT, "vnl-brax-imitation_amd", "data", "humanoid.npz")
-PARAMS = dict(solver="cg", iterations=6, ls_iterations=6)  # configs/env_config.yaml:1-8
-
-
-def _model():
-    return mjcf.CompiledModel.load(HUM_NPZ)
-
-
-def _clip(m, T=60, seed=0):
-    rng = np.random.default_rng(seed)
-    t = np.arange(T)[:, None] * 0.02
-    q = np.tile(np.asarray(m.arrays["qpos0"], dtype=np.float64), (T, 1))
-    q[:, 2] -= 0.002  # feet just into the floor: the capsule-floor pairs are active
-    q[:, 7:] += 0.08 * np.sin(2 * np.pi * (0.5 + rng.random(21)) * t + rng.random(21) * 6.28)
-    return pp.process_qpos(m, q)
-
-
-def _env(B, real="float", device="cpu", **kw):
-    from vnl_brax_imitation_amd.envs.humanoid import HumanoidTracking
-
-    m = _model()
-    import contextlib
-
-    with (H.hostsim_backend(real) if device == "cpu" else contextlib.nullcontext()):
-        return HumanoidTracking(PARAMS, clip_length=60, episode_length=20, reference_clip=_clip(m), model=m, num_envs=B,
-                                device=device, **kw)
 
 
 def _oracle(env, precision="f64"):

@@ -5,7 +5,6 @@ CPU tier: the float64 host build of the product source against the dense float64
 limit), the assembled Hessian against a NumPy one, the ant and the humanoid.  GPU tier: the rodent on the device against the
 float64 / float32 oracles following the product's decisions, determinism, graph capture and a short training run (the ant's
 Newton on the device: tests/test_ant_env.py::test_ant_env_newton_on_gpu)."""
-import copy
 import functools
 
 import numpy as np
@@ -13,29 +12,14 @@ import pytest
 import torch
 
 import helpers as H
+import hostsim_cases as HP
+import model_cases as M
 import parity as P
-import test_hostsim_parity as HP
+from model_cases import newton_model
+from model_cases import rodent_env as _rodent
 from vnl_brax_imitation_amd import configs, envs
-from vnl_brax_imitation_amd.model import mjcf
 
 CONFIGS = [(6, 6), (1, 4)]  # CG's counts, and the reference's Newton counts (configs/env_config.yaml:16-21)
-
-
-def newton_model(iterations, ls_iterations, base=None):
-    """A copy of the compiled model with the Newton options set, as envs/rodent.py _load_model sets them."""
-    m = copy.deepcopy(base if base is not None else H.model())
-    m.scalars.update(solver_newton=1, iterations=iterations, ls_iterations=ls_iterations)
-    return m
-
-
-def _rodent(B, m, device="cpu", real="double", **over):
-    from vnl_brax_imitation_amd.envs.rodent import RodentTracking
-
-    kw = dict(H.env_kwargs(), model=m, **over)
-    if device == "cpu":
-        with H.hostsim_backend(real):
-            return RodentTracking(H.reference_clip(), num_envs=B, device="cpu", **kw)
-    return RodentTracking(H.reference_clip(), num_envs=B, device=device, **kw)
 
 
 def _sections(env):
@@ -48,15 +32,15 @@ def _sections(env):
 def test_rodent_newton_float64_build_matches_oracle(it, ls):
     B = 16
     env = _rodent(B, newton_model(it, ls))
-    sf, noise, acts = HP._inputs(B)
+    sf, noise, acts = HP.parity_inputs(B)
     st = env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
     o = H.make_oracle(env, "f64")
     ost = o.env_reset(sf, noise)
-    e = HP._cmp(st, ost, B)
+    e = HP.parity_errors(st, ost, B)
     assert max(e.values()) < 1e-11, e
     st = env.step(st, torch.from_numpy(acts[0]))
     o.env_step(ost, acts[0])
-    e = HP._cmp(st, ost, B)
+    e = HP.parity_errors(st, ost, B)
     assert max(e.values()) < 1e-8, e  # the bound the CG route is held to (test_hostsim_parity)
     assert np.array_equal(st.done.numpy(), ost["done"])
     m = np.stack([st.metrics[k].numpy() for k in st.metrics], 1)
@@ -82,7 +66,7 @@ def test_rodent_newton_tree_hessian_assembly():
     """The Hessian the kernel factorised, rebuilt from its inverted L'DL factor in the debug image, against NumPy's
     qM + J' diag(D * (Jaref < 0)) J with qM / efc_J from the oracle at the same state and efc_D / Jaref from the image."""
     env = _sections(_rodent(1, newton_model(6, 6)))
-    sf, noise, _ = HP._inputs(1, seed=7)
+    sf, noise, _ = HP.parity_inputs(1, seed=7)
     env.reset(start_frame=torch.from_numpy(sf), noise=torch.from_numpy(noise))
     o = H.make_oracle(env, "f64")
     c = env.clip_arrays(0)
@@ -126,37 +110,24 @@ def test_rodent_newton_tree_hessian_assembly():
 
 
 def _ant_env(B):
-    from test_ant_env import ANT_NPZ, NEWTON, _clip
-
-    m = mjcf.CompiledModel.load(ANT_NPZ)
-    with H.hostsim_backend("double"):
-        return envs.get_environment("ant", params=NEWTON, clip_length=60, episode_length=20, reference_clip=_clip(m), model=m,
-                                    num_envs=B, device="cpu")
+    return M.ant_env(B, "double", params=M.NEWTON)
 
 
 def _humanoid_env(B):
-    from test_humanoid import _clip, _model
-    from vnl_brax_imitation_amd.envs.humanoid import HumanoidTracking
-
-    m = newton_model(1, 4, base=_model())
-    with H.hostsim_backend("double"):
-        return HumanoidTracking(dict(solver="newton", iterations=1, ls_iterations=4), clip_length=60, episode_length=20,
-                                reference_clip=_clip(m), model=m, num_envs=B, device="cpu")
+    return M.humanoid_newton_env(B, "double")
 
 
 @pytest.mark.parametrize("which", ["ant", "humanoid"])
 def test_small_models_newton_float64_build_matches_oracle(which):
     """The ant (its welded bodies folded) and the humanoid (eulerdamp off) with Newton 1 / 4: four control steps against the
     oracle, whose dense Cholesky is the independent check of the tree-sparse factorisation."""
-    from test_ant_env import _oracle
-
     B = 6
     env = (_ant_env if which == "ant" else _humanoid_env)(B)
     env.debug(True)
     nu, nq = env.action_size, int(env.sys.scalars["nq"])
     sf = np.random.default_rng(5).integers(0, 30, B).astype(np.int32)
     st = env.reset(start_frame=torch.from_numpy(sf))
-    o = _oracle(env)
+    o = H.make_oracle(env)
     ost = o.env_reset(sf, np.zeros((B, nq)))
     rng = np.random.default_rng(4)
     moved = 0.0
@@ -263,7 +234,6 @@ def test_rodent_newton_rollout_deterministic_on_gpu():
 
 @pytest.mark.gpu
 def test_rodent_newton_graphed_unroll_equals_eager_on_gpu():
-    from test_fused_rollout import _setup
     from vnl_brax_imitation_amd.ppo_imitation import acting
 
     dev = torch.device("cuda:0")
@@ -271,7 +241,7 @@ def test_rodent_newton_graphed_unroll_equals_eager_on_gpu():
     B, T, extra = 130, 6, ("truncation", "traj")
     out = []
     for graphed in (False, True):
-        env, policy = _setup(B, False, 4, make_env, dev)
+        env, policy = H.unroll_setup(B, False, 4, make_env, dev)
         torch.manual_seed(123)
         state = env.reset(torch.Generator().manual_seed(5))
         key = torch.Generator(device=dev).manual_seed(11)

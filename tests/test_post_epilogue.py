@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 import helpers as H
+import model_cases as M
 import post_epilogue_cases as PE
 from vnl_brax_imitation_amd import _lib
 
@@ -30,8 +31,6 @@ def test_unroll_with_epilogue_equals_the_two_launch_unroll():
 def test_an_env_that_works_on_the_state_after_its_step_keeps_the_two_launches():
     """AntTracking.step assembles the observation AFTER the kernel: the post-processing must see it, so the unroll must not
     take the epilogue there -- switch on and off give the same unroll, and no step carries a descriptor."""
-    import test_ant_env as A
-
     dev, seen = torch.device("cpu"), []
 
     def hook(base):
@@ -43,7 +42,7 @@ def test_an_env_that_works_on_the_state_after_its_step_keeps_the_two_launches():
 
         base.step = step
 
-    runs = [PE.unroll_case(lambda: A._env(5), dev, epilogue, hook=hook) for epilogue in (False, True)]
+    runs = [PE.unroll_case(lambda: M.ant_env(5), dev, epilogue, hook=hook) for epilogue in (False, True)]
     PE.assert_unrolls_same(*runs)
     assert seen == [False] * 6
 

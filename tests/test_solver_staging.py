@@ -6,73 +6,24 @@ former reads (-DVNL_SOLVER_PLAIN, the `plain` variant of csrc/build.py) must giv
 What this file covers: the LDS tables and the staged friction only.  The register part is device code (VNL_SOLVE_REGS is 0 in a
 host build, which reads blk_tab and dof_limrow where they are): `with_solve_regs`, `limrow_of` and the `sr.blk` path of
 `blk_apply` are covered by tests/test_gpu_solver_staging.py alone."""
-import functools
-import os
-import subprocess
-
 import numpy as np
 import pytest
-import torch
 
-import domain_cases as D
 import helpers as H
-import test_solver_tail as T
-from vnl_brax_imitation_amd import _lib
+import hostsim_cases as HC
 
 STEPS = 4
 B = 4
-
-
-@functools.lru_cache(maxsize=None)
-def _plain_library(real):
-    src = os.path.join(H.ROOT, "vnl-brax-imitation_amd", "csrc")
-    out = os.path.join(H.ROOT, "tests", "hostsim", "_build", f"libvnl_hostsim_{real}_plain.so")
-    deps = [os.path.join(src, f) for f in os.listdir(src) if f.endswith((".h", ".hip"))]
-    deps += [os.path.join(H.ROOT, "include", "vnl.h"), os.path.join(H.ROOT, "tests", "hostsim", "stub", "hip", "hip_runtime.h")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", f"-DVNL_REAL={real}", "-DVNL_SOLVER_PLAIN",
-                               "-I" + os.path.join(H.ROOT, "tests", "hostsim", "stub"), "-x", "c++",
-                               os.path.join(src, "vnl_lib.hip"), "-o", out])
-    return _lib.load_library(out, env_only=True)
-
-
-def _rodent_friction(n):
-    """A rodent whose envs each have their own friction (the randomised instantiation: friction staged per env)."""
-    env, nu = T.MODELS["rodent_cg_6_6"](n)
-    dom = D.random_domain(env.sys, n, 21)
-    return env.with_domain({"cg_friction": dom["cg_friction"]}), nu
-
-
-MODELS = dict(T.MODELS, rodent_friction_domain=_rodent_friction)
-
-
-def _rollout(library, real, make):
-    dtype = torch.float64 if real == "double" else torch.float32
-    with H.backend(library, dtype):
-        env, nu = make(B)
-        rng = np.random.default_rng(3)
-        st = env.reset(5)
-        snaps = [T._outputs(st)]
-        for _ in range(STEPS):
-            act = torch.from_numpy(np.clip(0.3 * rng.standard_normal((B, nu)), -1, 1)).to(dtype)
-            st = env.step(st, act)
-            snaps.append(T._outputs(st))
-    return env, snaps
+MODELS = dict(HC.MODELS, rodent_friction_domain=HC.rodent_friction)
 
 
 @pytest.mark.parametrize("real", ["float", "double"])
 @pytest.mark.parametrize("name", list(MODELS))
 def test_staged_solver_constants_change_no_bit(name, real):
-    _, staged = _rollout(H.hostsim_library(real), real, MODELS[name])
-    _, plain = _rollout(_plain_library(real), real, MODELS[name])
-    moved = False
-    for t, (a, b) in enumerate(zip(staged, plain)):
-        assert a.keys() == b.keys()
-        for k in a:
-            assert torch.equal(a[k], b[k]), (name, real, t, k)
-        moved = moved or (t > 0 and not torch.equal(a["ps.qpos"], staged[0]["ps.qpos"]))
-    assert moved
+    # (env and rollout inside the backend: the friction case's with_domain must bind to the same library)
+    _, staged = HC.host_rollout(H.hostsim_library(real), real, MODELS[name], B, STEPS, step_in_backend=True)
+    _, plain = HC.host_rollout(H.hostsim_library(real, "plain"), real, MODELS[name], B, STEPS, step_in_backend=True)
+    HC.same_rollouts(staged, plain, (name, real))
 
 
 def test_rodent_layout_keeps_eight_workgroups_per_cu():

@@ -14,7 +14,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 import vnl_brax_imitation_amd  # noqa: E402,F401
-from test_gpu_ppo_update import HP, _make  # noqa: E402
+from ppo_update_cases import HP  # noqa: E402
+from ppo_update_cases import make as _make  # noqa: E402
 
 
 def main():

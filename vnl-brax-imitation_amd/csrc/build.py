@@ -44,24 +44,25 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          same adds on the same operands, the same bits on every output; tests/test_gpu_xlane_plain.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
+#   nospec -DVNL_NO_SPEC: the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones
+#          must agree bit for bit (tests/test_gpu_spill.py)
+#
+# The product holds its env kernels to two waves per SIMD: the specialised instantiations, every bound a constant, are
+# unrolled further by the compiler and would otherwise take a 257th register -- half the occupancy.  The diagnostic and
+# regression variants carry extra code: held to the same two waves so that their timings stay comparable.
+TWO_WAVES = "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"
+_DEFINES = {"prof": "VNL_PROFILE", "knobs": "VNL_STAGE_KNOBS", "noblk": "VNL_NO_BLK", "tail": "VNL_SOLVER_TAIL",
+            "plain": "VNL_SOLVER_PLAIN", "vmemplain": "VNL_VMEM_PLAIN", "ldsplain": "VNL_LDS_PLAIN",
+            "sgprplain": "VNL_SGPR_PLAIN", "xlaneplain": "VNL_XLANE_PLAIN", "nospec": "VNL_NO_SPEC"}
 VARIANTS = {
-    # (the product holds its env kernels to two waves per SIMD: the specialised instantiations, every bound a constant, are
-    # unrolled further by the compiler and would otherwise take a 257th register -- half the occupancy)
-    "product": ("libvnl.so", ["-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    # (the diagnostic variants carry extra code: held to the product's two waves per SIMD so that their timings stay comparable)
-    "prof": ("libvnl_prof.so", ["-DVNL_PROFILE", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "knobs": ("libvnl_knobs.so", ["-DVNL_STAGE_KNOBS", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    "product": ("libvnl.so", [TWO_WAVES]),
     "spill": ("libvnl_spill.so", ["-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(4,4)))"]),
-    "noblk": ("libvnl_noblk.so", ["-DVNL_NO_BLK", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "tail": ("libvnl_tail.so", ["-DVNL_SOLVER_TAIL", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "plain": ("libvnl_plain.so", ["-DVNL_SOLVER_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "vmemplain": ("libvnl_vmemplain.so", ["-DVNL_VMEM_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "ldsplain": ("libvnl_ldsplain.so", ["-DVNL_LDS_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "sgprplain": ("libvnl_sgprplain.so", ["-DVNL_SGPR_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    "xlaneplain": ("libvnl_xlaneplain.so", ["-DVNL_XLANE_PLAIN", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
-    # the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones must agree bit for bit
-    "nospec": ("libvnl_nospec.so", ["-DVNL_NO_SPEC", "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"]),
+    **{v: (f"libvnl_{v}.so", ["-D" + d, TWO_WAVES]) for v, d in _DEFINES.items()},
 }
+# What the driver entry builds (__graft_entry__.build): the product and the regression builds the tests load.  A new
+# regression build is a paragraph above, an entry of _DEFINES and a name here; its device test is a few calls into
+# tests/variant_cases.py, its host test (tests/helpers.py HOSTSIM_VARIANTS) into tests/hostsim_cases.py.
+DRIVER_VARIANTS = ("product", "spill", "noblk", "nospec", "tail", "plain", "vmemplain", "ldsplain", "sgprplain", "xlaneplain")
 ENV_KERNELS = ("vnl_step_kernel", "vnl_reset_kernel", "vnl_reset_done_kernel")
 
 
@@ -130,14 +131,11 @@ def build(force: bool = False, verbose: bool = False, profile: bool = False, kno
         sys.stderr.write(r.stderr)
         raise subprocess.CalledProcessError(r.returncode, cmd)
 
-    class _R:  # (the check below reads the remarks of all objects, cached or not)
-        stderr = remarks
-    r = _R()
     # Register budget of the env kernels: a PERFORMANCE check (two waves per SIMD and no private-memory stack are what
     # the measured numbers assume), not a correctness one -- the spill variant runs the parity tests with hundreds of bytes of
     # scratch per lane.  Fails closed: if the compiler's remarks for the env kernels are not found, the build is
     # rejected rather than waved through.
-    usage = resource_usage(r.stderr)
+    usage = resource_usage(remarks)  # (of all objects, cached or not)
     seen = {k: [u for n, u in usage.items() if k in n] for k in ENV_KERNELS}
     missing = [k for k, v in seen.items() if not v or "Occupancy [waves/SIMD]" not in v[0]]
     if missing:
