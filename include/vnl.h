@@ -294,7 +294,8 @@ int vnl_env_set_domain(vnl_env* env, const vnl_domain* domain, void* stream);
  * lo > 0, damping and armature lo >= 0, and lo[f] / hi[f] are both given or both null.  An env without a four-field domain
  * gets its tables at the compiled values and runs the randomised kernels from then on; an env with vnl_env_set_domain
  * values keeps them until its first redraw.  A later vnl_env_set_domain overwrites the tables, not the ranges;
- * vnl_env_set_domain(null) also clears the ranges.  The body tables (vnl_env_set_body_domain) are never redrawn.
+ * vnl_env_set_domain(null) also clears the ranges.  The body tables (vnl_env_set_body_domain) are redrawn only
+ * under ranges of their own (vnl_env_set_body_domain_ranges below).
  * vnl_env_redraw_domain is the same device function as a launch of its own -- the domain of the FIRST episode
  * (initial = 1: a block range of its own, so that it differs from a reset at the same counter) and the tests' handle on the
  * draw: seed, step_base, step_offset and env_offset of the descriptor are read; a null mask = every env.  VNL_ERR_ARG
@@ -331,6 +332,48 @@ typedef struct vnl_body_domain {
   const double *body_mass, *body_inertia, *body_ipos;
 } vnl_body_domain;
 int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* domain, void* stream);
+
+/* A new BODY domain per episode (opt-in): per-element bounds of the three fields of vnl_body_domain, stored with the env.  With
+ * ranges set, vnl_env_reset_done / vnl_env_reset_done_weighted draw mass, moments and centre of mass of every env they reset
+ * anew inside the reset kernel -- at the place of the four-field redraw (vnl_domain_ranges above) and after it, before the noise
+ * and integer draws and the reset body -- and derive the four body tables on the device by the fold the host runs
+ * (csrc/vnl_inertial.h: float64, no fused multiply-add): the bits vnl_env_set_body_domain produces from the same float64 values.
+ * The draw continues the block range of vnl_domain_ranges with the field indices f = 4 body_mass, 5 body_inertia, 6 body_ipos;
+ * element j of the flattened field ([nbody], [nbody][3], [nbody][3]):
+ *   counter = (0x40000000 + initial * 0x20000000 + f * 0x00100000 + j / 4, env_offset + e, step low 32 bits,
+ *              (step >> 32) << 2 | 3), word j % 4; a SHARED field: word 0 of block j / 4 = 0 for every element
+ *   v = lo[j] + u * (hi[j] - lo[j]), u = (x + 0.5) * 2^-32   exactly as for vnl_domain_ranges
+ * With VNL_BODY_RANGES_INERTIA_WITH_MASS moment (b, k) takes the word of body b's MASS draw (the shared mass word if the mass
+ * field is shared): the triangle inequality of the moments is not checked, and bounds for mass and moments that are the same
+ * multiples of the compiled values then scale a body like a change of density -- a body that was physical stays physical.
+ * Without the flag the moments are drawn independently.  Row 0 (the world body) is never drawn.  A field without bounds keeps,
+ * per env, the values vnl_env_set_body_domain gave it (else the compiled ones).  ppo_imitation/philox.py (body_domain_draws)
+ * restates the draw.
+ * The contract of vnl_env_set_domain_ranges: the call waits for `stream`, validates on the host first (VNL_ERR_ARG with the
+ * field's name, nothing launched and nothing changed) and copies the bounds and what the fold needs into one library-owned
+ * device buffer; VNL_ERR_BLOB for body_inertia bounds on a model without body_inertia / body_iquat.  Valid: every value finite,
+ * lo <= hi, mass and moment lo >= 0, lo[f] / hi[f] both given or both null, the flag only with mass bounds -- and, because the
+ * kernel does not validate, a sufficient condition for every draw to pass vnl_env_set_body_domain's own checks: at the LOWER
+ * bounds every dynamic body that carries dofs has a member mass sum > 0 and a member whose three moments are > 0, and the total
+ * mass is > 0.  (Masses only grow from their lower bounds, so every fused mass and the total stay > 0.  The fused inertia about
+ * the fused centre of mass is the sum over the members of R I R' plus a parallel-axis term m (|d|^2 1 - d d'), each positive
+ * semi-definite; I of the member with three positive moments is R(iquat) diag(moments) R(iquat)' up to the rounding of the
+ * compiled full inertia, positive definite -- so the sum is, and its diagonal is positive.)
+ * An env without a body domain gets its body tables at the compiled values and runs the randomised kernels from then on.  A
+ * later vnl_env_set_body_domain overwrites tables, not ranges; vnl_env_set_body_domain(null) clears its part AND these ranges;
+ * vnl_env_set_domain(null) clears the four-field ranges only.  vnl_env_redraw_domain draws whichever of the two range sets the
+ * env has, and fails with "no ranges" only when it has neither. */
+#define VNL_BODY_RANGES_INERTIA_WITH_MASS 1u
+typedef struct vnl_body_domain_ranges {
+  /* fields in the order of vnl_body_domain: body_mass [nbody], body_inertia [nbody][3], body_ipos [nbody][3] over the
+     bodies AS GIVEN; DEVICE float64, ABSOLUTE bounds per element; lo[f] and hi[f] both null: field f is never redrawn.
+     Row 0 (the world body) is never drawn: it keeps the compiled values, as under vnl_env_set_body_domain. */
+  const double* lo[3];
+  const double* hi[3];
+  uint32_t shared; /* bit f: ONE uniform per (env, episode) for the whole field f */
+  uint32_t flags;  /* VNL_BODY_RANGES_INERTIA_WITH_MASS: moment (b, k) takes the uniform of body b's MASS draw */
+} vnl_body_domain_ranges;
+int vnl_env_set_body_domain_ranges(vnl_env*, const vnl_body_domain_ranges*, void* stream); /* null clears */
 
 /* Bisection hooks.  The per-env working set lives in LDS; with debug on, every reset/step
  * also copies it to a device dump [num_envs][row_stride]: enable = 1 at the end of the kernel,

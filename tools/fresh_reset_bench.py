@@ -25,6 +25,12 @@ kernels, the tables never written) without and with ranges on all four fields (w
 friction, gain, damping and armature anew inside the reset launch), alternated in this one process; with --per-step the
 reset launch of every step and the launch alone at fixed shares, for both.  --mode fresh_domain is the first of these legs on
 its own (no new entry point is called: it also runs against an older library, for the comparison of the default paths).
+
+--body-ranges: the legs are fresh mode on an identity-BODY-domain env (with_body_domain of the compiled values) without and
+with body ranges (with_body_domain_ranges of body_domain_ranges_scaled: mass and moments x [0.7, 1.3] on the mass's uniform,
+ipos -/+ 0.2 |ipos|: every reset env draws its bodies anew and folds its welded bodies in float64 inside the reset launch),
+alternated in this one process; with --per-step the reset launch of every step and the launch alone at fixed shares (none,
+64, 512, all envs), for both.
 """
 from __future__ import annotations
 
@@ -70,6 +76,7 @@ def main() -> None:
     ap.add_argument("--per-step", action="store_true", help="also time every control step of one eager fused unroll in fresh mode")
     ap.add_argument("--start-priority", action="store_true", help="legs: fresh mode without and with a StartPriority")
     ap.add_argument("--domain-ranges", action="store_true", help="legs: fresh mode on an identity-domain env without and with ranges")
+    ap.add_argument("--body-ranges", action="store_true", help="legs: fresh mode on an identity-body-domain env without and with body ranges")
     args = ap.parse_args()
 
     import numpy as np
@@ -87,6 +94,8 @@ def main() -> None:
         modes = ("fresh", "fresh_priority")
     if args.domain_ranges:
         modes = ("fresh_domain", "fresh_ranges")
+    if args.body_ranges:
+        modes = ("fresh_body", "fresh_body_ranges")
     priorities = {}
 
     def setup(mode):
@@ -100,6 +109,15 @@ def main() -> None:
 
                 base = base.with_domain_ranges(domain_ranges_scaled(base.sys, friction=(0.5, 1.5), gain=(0.7, 1.3),
                                                                     damping=(0.5, 2.0), armature=(0.5, 2.0)))
+        if mode in ("fresh_body", "fresh_body_ranges"):
+            import body_domain_cases as BD
+
+            base = base.with_body_domain(BD.identity(base.sys, B))
+            if mode == "fresh_body_ranges":
+                from vnl_brax_imitation_amd.envs.rodent import body_domain_ranges_scaled
+
+                base = base.with_body_domain_ranges(body_domain_ranges_scaled(base.sys, mass=(0.7, 1.3), ipos=(-0.2, 0.2)),
+                                                    inertia_with_mass=True)
         ep = EpisodeWrapper(base, episode_length=150, action_repeat=1)
         # (the default mode is constructed as before the keyword existed: this file also runs against an older library)
         if mode == "fresh_priority":
@@ -179,6 +197,8 @@ def main() -> None:
             torch.cuda.synchronize(dev)
             us.append(e0.elapsed_time(e1) * 1e3)
         out["update_kernel_us_at_15040_cells"] = round(float(np.median(us[3:])), 1)
+    elif args.body_ranges:
+        out["body_ranges_minus_body_domain_ms"] = round(med["fresh_body_ranges"] - med["fresh_body"], 5)
     elif args.domain_ranges:
         out["ranges_minus_domain_ms"] = round(med["fresh_ranges"] - med["fresh_domain"], 5)
     elif len(modes) == 2:
@@ -214,7 +234,7 @@ def main() -> None:
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
         logs = [(state.obs, torch.empty_like(state.obs)), (state.info["traj"], torch.empty_like(state.info["traj"]))]
         alone = {}
-        for share in (0.0, 1.0 / 64, 0.125, 1.0):
+        for share in (0.0, 64.0 / B, 512.0 / B, 1.0) if args.body_ranges else (0.0, 1.0 / 64, 0.125, 1.0):
             mask = (torch.arange(B, device=dev) < round(share * B)).float()
             us = []
             for k in range(23):

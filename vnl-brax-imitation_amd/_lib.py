@@ -170,6 +170,11 @@ class Domain(C.Structure):  # include/vnl.h: vnl_domain (float64 device pointers
 class DomainRanges(C.Structure):  # include/vnl.h: vnl_domain_ranges (float64 device pointers [n_f], fields in the order of vnl_domain)
     _fields_ = [("lo", C.c_void_p * 4), ("hi", C.c_void_p * 4), ("shared", C.c_uint32), ("pad_", C.c_uint32)]
 
+BODY_RANGES_INERTIA_WITH_MASS = 1  # include/vnl.h: VNL_BODY_RANGES_INERTIA_WITH_MASS
+
+class BodyDomainRanges(C.Structure):  # include/vnl.h: vnl_body_domain_ranges (float64 device pointers, fields in the order of vnl_body_domain)
+    _fields_ = [("lo", C.c_void_p * 3), ("hi", C.c_void_p * 3), ("shared", C.c_uint32), ("flags", C.c_uint32)]
+
 class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device pointers, [num_envs][nbody (x3)]; null = the model's value)
     _fields_ = [(n, C.c_void_p) for n in ("body_mass", "body_inertia", "body_ipos")]
 
@@ -182,6 +187,7 @@ EXPORTS = (
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
     "vnl_env_set_domain", "vnl_env_set_body_domain", "vnl_env_set_domain_ranges", "vnl_env_redraw_domain",
+    "vnl_env_set_body_domain_ranges",
     "vnl_prediction_corr_plan", "vnl_prediction_corr",
 )
 _HIP_ONLY = ("vnl_policy_", "vnl_ppo_update_", "vnl_ppo_minibatch_", "vnl_prediction_corr")  # not in the test-only host simulation
@@ -217,6 +223,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.vnl_env_set_body_domain.argtypes = [vp, C.POINTER(BodyDomain), vp]
     lib.vnl_env_set_domain_ranges.argtypes = [vp, C.POINTER(DomainRanges), vp]
     lib.vnl_env_redraw_domain.argtypes = [vp, vp, C.POINTER(ResetNoise), C.c_int32, vp]
+    lib.vnl_env_set_body_domain_ranges.argtypes = [vp, C.POINTER(BodyDomainRanges), vp]
     lib.vnl_rollout_post.argtypes = [C.POINTER(PostDesc), C.c_int32, vp]
     lib.vnl_ppo_head.argtypes = [C.POINTER(PPOHeadArgs), vp, vp]
     lib.vnl_gather_rows.argtypes = [C.POINTER(GatherDesc), vp]

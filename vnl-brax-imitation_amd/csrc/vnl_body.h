@@ -35,6 +35,7 @@
 #endif
 
 #include "vnl_types.h"
+#include "vnl_inertial.h"
 
 #ifndef VNL_HD
 #define VNL_HD __device__ __forceinline__
@@ -3332,7 +3333,81 @@ struct EnvWaveT {
     }
   }
 
-  // Order: the start-priority counting (it reads the finished episode), the domain redraw, the noise and integer draws, the
+  // The BODY domain of THIS env drawn anew (include/vnl.h: vnl_body_domain_ranges; randomised instantiations only): mass,
+  // principal moments and centre of mass of the bodies AS GIVEN, fields 4, 5, 6 of redraw_domain's block range (element j of
+  // the flattened field = word j % 4 of block j / 4; a SHARED field word 0 of block 0; with INERTIA_WITH_MASS moment (b, k)
+  // takes the word of body b's mass), then the four tables par_row<>() / total_mass_inv() read, as vnl_env_set_body_domain
+  // derives them from the same float64 values -- the fold of csrc/vnl_inertial.h, the one the host runs:
+  //   1. a lane per body as given draws its seven elements (a field without bounds: this env's row of brng.raw; body 0 is
+  //      never drawn), forms its full inertia and its record of the fold (VNL_FOLD_REC doubles), and stores the record to this
+  //      env's slice of brng.stage -- records cross lanes;
+  //   2. behind a join of its own, a lane per DYNAMIC body sums the records of its members in ascending order, shifts to the
+  //      fused centre of mass, stores its rows of the three tables as (vreal) and its fused mass to the stage;
+  //   3. behind a second join lane 0 sums the fused masses in ascending order: 1 / total mass.
+  // A model without welded bodies passes through as on the host: step 1 stores the tables, step 2 is skipped.
+  // Plain vector stores through the WRITABLE views of brng; a VNL_SYNC_GLOBAL() must follow before par_row<>() reads them.
+  VNL_HD void redraw_body_domain(uint32_t key0, uint32_t key1, uint32_t c1, uint32_t c2, uint32_t c3, int initial) const {
+    if constexpr (SP::dom) {
+      const VNL_CAS DevBodyRanges& r = kc->brng;
+      const int nb = MI(nbody_out), nd = MI(nbody);
+      const uint32_t base = 0x40000000u + (initial ? 0x20000000u : 0u);
+      const uint32_t shared = r.shared;
+      const bool with_mass = (r.flags & VNL_BODY_RANGES_INERTIA_WITH_MASS) != 0;
+      const double* raw = r.raw + (size_t)e * 7 * nb;
+      double* recs = r.stage + (size_t)e * (VNL_FOLD_REC * nb + nd);
+      double* fused = recs + (size_t)VNL_FOLD_REC * nb;
+      const double *lo_m = r.lo[0], *hi_m = r.hi[0], *lo_i = r.lo[1], *hi_i = r.hi[1], *lo_p = r.lo[2], *hi_p = r.hi[2];
+      auto word = [&](int f, int j) {
+        const bool one = (shared >> (f - 4)) & 1u;
+        const uint32_t b0 = base + (uint32_t)f * 0x00100000u;
+        uint32_t x[4];
+        philox4x32_10(one ? b0 : b0 + (uint32_t)(j >> 2), c1, c2, c3, key0, key1, x);
+        const int q = one ? 0 : (j & 3);
+        return q == 0 ? x[0] : (q == 1 ? x[1] : (q == 2 ? x[2] : x[3]));
+      };
+      VNL_FOR(b, nb) {
+        double m = raw[b], mom[3], ip[3], full[9];
+        for (int k = 0; k < 3; k++) mom[k] = raw[nb + 3 * b + k], ip[k] = raw[4 * nb + 3 * b + k];
+        if (b > 0) {
+          uint32_t wm = 0;
+          if (lo_m) wm = word(4, b), m = vnl_domain_value(lo_m[b], hi_m[b], wm);
+          if (lo_i)
+            for (int k = 0; k < 3; k++) mom[k] = vnl_domain_value(lo_i[3 * b + k], hi_i[3 * b + k], with_mass ? wm : word(5, 3 * b + k));
+          if (lo_p)
+            for (int k = 0; k < 3; k++) ip[k] = vnl_domain_value(lo_p[3 * b + k], hi_p[3 * b + k], word(6, 3 * b + k));
+        }
+        vnl_full_inertia(r.ifull0 + 9 * b, r.R_iq0 + 9 * b, mom, r.inertia0 + 3 * b, full);
+        if (nd == nb) {
+          double i6[6];
+          vnl_pack_inertia6(full, i6);
+          r.body_mass[(size_t)e * nd + b] = (vreal)m, fused[b] = m;
+          for (int k = 0; k < 3; k++) r.body_ipos[((size_t)e * nd + b) * 3 + k] = (vreal)ip[k];
+          for (int k = 0; k < 6; k++) r.body_inertia6[((size_t)e * nd + b) * 6 + k] = (vreal)i6[k];
+        } else {
+          double rec[VNL_FOLD_REC];
+          vnl_fold_member(r.R_out + 9 * b, r.out_pos + 3 * b, m, ip, full, rec);
+          for (int k = 0; k < VNL_FOLD_REC; k++) recs[VNL_FOLD_REC * b + k] = rec[k];
+        }
+      }
+      if (nd != nb) {
+        VNL_SYNC_GLOBAL();  // (the records: stored by the lanes of the bodies as given, read by those of the dynamic bodies)
+        VNL_FOR(d, nd) {
+          double acc[VNL_FOLD_ACC], nip[3], nI[9], i6[6];
+          const int m0 = r.mem_start[d], m1 = r.mem_start[d + 1];
+          vnl_fold_gather(r.mem + m0, m1 - m0, recs, acc);
+          vnl_fold_finish(acc, recs + VNL_FOLD_REC * r.body_out[d] + 13, nip, nI);
+          vnl_pack_inertia6(nI, i6);
+          r.body_mass[(size_t)e * nd + d] = (vreal)acc[0], fused[d] = acc[0];
+          for (int k = 0; k < 3; k++) r.body_ipos[((size_t)e * nd + d) * 3 + k] = (vreal)nip[k];
+          for (int k = 0; k < 6; k++) r.body_inertia6[((size_t)e * nd + d) * 6 + k] = (vreal)i6[k];
+        }
+      }
+      VNL_SYNC_GLOBAL();  // (the fused masses)
+      VNL_SERIAL { r.total_mass_inv[e] = (vreal)vnl_total_mass_inv(fused, nd); }
+    }
+  }
+
+  // Order: the start-priority counting (it reads the finished episode), the domain redraws, the noise and integer draws, the
   // reset body -- whose forward pass, and the warm start it leaves, belong to the new domain.
   VNL_HD void reset_fresh(const ResetDoneArgs& a, int* trace_base) const {
     const int nq = MI(nq), nblk = (nq + 3) >> 2;
@@ -3340,9 +3415,12 @@ struct EnvWaveT {
     const uint32_t c1 = a.env0 + (uint32_t)e, c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
     bool counted = false;
     if constexpr (SP::dom) {
-      if (kc->rng.on) {
+      const int on = kc->rng.on;
+      if (on) {
         if (a.prio.cdf) prio_count(a), counted = true;
-        redraw_domain(a.key0, a.key1, c1, c2, c3, 0);  // (the join below, before reset_core, stands between these stores and par<F>())
+        // (the join below, before reset_core, stands between these stores and par<F>() / par_row<F>())
+        if (on & VNL_RANGES_FOUR) redraw_domain(a.key0, a.key1, c1, c2, c3, 0);
+        if (on & VNL_RANGES_BODY) redraw_body_domain(a.key0, a.key1, c1, c2, c3, 0);
       }
     }
     vreal* nz = a.noise + (size_t)e * nq;

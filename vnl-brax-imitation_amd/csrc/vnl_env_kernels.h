@@ -144,8 +144,9 @@ __global__ void VNL_ENV_KERNEL vnl_reset_done_kernel(const KernelConsts* kc, Dev
 }
 
 // The domain redraw of EnvWaveT::reset_fresh as a launch of its own (vnl_env_redraw_domain: the first episode's domain, and
-// what the tests compare the fused redraw with): the envs whose mask is set, or every env with a null mask.  Randomised
-// instantiations only; no LDS, no state.
+// what the tests compare the fused redraw with): the envs whose mask is set, or every env with a null mask; the four-field
+// ranges, the body ranges (EnvWaveT::redraw_body_domain), or both, as the env has them.  Randomised instantiations only; no
+// LDS, no state.
 template <class SP>
 __global__ void __launch_bounds__(64) vnl_redraw_domain_kernel(const KernelConsts* kc, const float* mask, const int64_t* step_base,
                                                                int64_t step_offset, uint32_t key0, uint32_t key1, uint32_t env0,
@@ -156,5 +157,8 @@ __global__ void __launch_bounds__(64) vnl_redraw_domain_kernel(const KernelConst
   const DevState none{};
   EnvWaveT<SP> w{k->m, k->ev, none, k->L, nullptr, e, lane, k, nullptr};
   const int64_t step = *step_base + step_offset;
-  w.redraw_domain(key0, key1, env0 + e, (uint32_t)step, ((uint32_t)(step >> 32) << 2) | 3u, initial);
+  const uint32_t c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
+  const int on = k->rng.on;  // (whichever of the two range sets the env has)
+  if (on & VNL_RANGES_FOUR) w.redraw_domain(key0, key1, env0 + e, c2, c3, initial);
+  if (on & VNL_RANGES_BODY) w.redraw_body_domain(key0, key1, env0 + e, c2, c3, initial);
 }

@@ -15,6 +15,7 @@
 
 #include "../../include/vnl.h"
 #include "vnl_body.h"
+#include "vnl_inertial.h"
 
 // ----------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -127,7 +128,13 @@ struct vnl_env {
   // vnl_env_set_body_domain: the inertial fields of the model AS GIVEN and the fold of its welded bodies, kept from the upload
   struct FuseMap* fmap = nullptr;
   std::vector<double> mass0, ipos0, ifull0, inertia0, iquat0;  // (inertia0 / iquat0 empty: the blob does not carry them)
+  std::vector<double> R_iq0;                                   // [nbody as given][9] rotation matrix of iquat0 (qmat_d), once
   std::vector<int> dyn_dofnum;                                 // dofs of every dynamic body
+  // vnl_env_set_body_domain_ranges: one device buffer (bounds, what the fold needs, per-env raw fields and staging; see
+  // body_ranges_layout) and the host copy of the raw fields vnl_env_set_body_domain was given ([B][n] each, empty: compiled)
+  char* brng_buf = nullptr;
+  int has_body_ranges = 0;
+  std::vector<double> body_raw[3];
   std::vector<void*> allocs;
   std::map<std::string, std::pair<int, int>> sections;  // name -> (offset, count)
 };
@@ -177,6 +184,8 @@ struct FuseMap {
   int nb_out = 0;
   std::vector<int> out_dyn, body_out;
   std::vector<double> out_pos, out_quat;
+  std::vector<int> mem_start, mem;  // the members of every dynamic body, ascending (CSR): what fuse_inertial gathers over
+  std::vector<double> R_out;        // [nb_out][9] the rotation matrix of out_quat
 };
 static void qmul_d(const double* a, const double* b, double* o) {
   o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
@@ -206,54 +215,27 @@ static void fuse_inertial(const FuseMap& fmr, int nd, const double* mass, const 
     M.assign(mass, mass + nb), nip.assign(ipos, ipos + 3 * (size_t)nb), nI.assign(ifull, ifull + 9 * (size_t)nb);
     return;
   }
-  M.assign(nd, 0.0);
-  std::vector<double> mc(3 * (size_t)nd, 0.0), J(9 * (size_t)nd, 0.0);
-  for (int b = 0; b < nb; b++) {
-    const int dyn = fm->out_dyn[b];
-    double R[9], c[3], t[3];
-    qmat_d(&fm->out_quat[4 * (size_t)b], R), mulv_d(R, &ipos[3 * (size_t)b], t);
-    for (int k = 0; k < 3; k++) c[k] = fm->out_pos[3 * (size_t)b + k] + t[k];
-    const double m = mass[b], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    M[dyn] += m;
-    for (int k = 0; k < 3; k++) mc[3 * (size_t)dyn + k] += m * c[k];
-    const double* I = &ifull[9 * (size_t)b];
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 3; q++) {
-        double v = 0;  // (R I R')(r, q)
-        for (int a = 0; a < 3; a++)
-          for (int e = 0; e < 3; e++) v += R[3 * r + a] * I[3 * a + e] * R[3 * q + e];
-        J[9 * (size_t)dyn + 3 * r + q] += v + m * ((r == q ? cc : 0.0) - c[r] * c[q]);
-      }
-  }
-  nip.assign(3 * (size_t)nd, 0.0), nI.assign(9 * (size_t)nd, 0.0);
+  // (csrc/vnl_inertial.h: a record per body as given, then per dynamic body the sum over its members in ascending order)
+  std::vector<double> recs((size_t)VNL_FOLD_REC * nb);
+  for (int b = 0; b < nb; b++)
+    vnl_fold_member(&fm->R_out[9 * (size_t)b], &fm->out_pos[3 * (size_t)b], mass[b], &ipos[3 * (size_t)b], &ifull[9 * (size_t)b],
+                    &recs[(size_t)VNL_FOLD_REC * b]);
+  M.assign(nd, 0.0), nip.assign(3 * (size_t)nd, 0.0), nI.assign(9 * (size_t)nd, 0.0);
   for (int dyn = 0; dyn < nd; dyn++) {
-    double c[3] = {0, 0, 0};
-    if (M[dyn] > 0)
-      for (int k = 0; k < 3; k++) c[k] = mc[3 * (size_t)dyn + k] / M[dyn];
-    else
-      for (int k = 0; k < 3; k++) c[k] = ipos[3 * (size_t)fm->body_out[dyn] + k];
-    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    for (int k = 0; k < 3; k++) nip[3 * (size_t)dyn + k] = c[k];
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 3; q++) nI[9 * (size_t)dyn + 3 * r + q] = J[9 * (size_t)dyn + 3 * r + q] - M[dyn] * ((r == q ? cc : 0.0) - c[r] * c[q]);
+    double acc[VNL_FOLD_ACC];
+    vnl_fold_gather(&fm->mem[fm->mem_start[dyn]], fm->mem_start[dyn + 1] - fm->mem_start[dyn], recs.data(), acc);
+    M[dyn] = acc[0];
+    vnl_fold_finish(acc, &ipos[3 * (size_t)fm->body_out[dyn]], &nip[3 * (size_t)dyn], &nI[9 * (size_t)dyn]);
   }
 }
 // body_inertia_full [nb][9] -> body_inertia6 [nb][6]: xx yy zz xy xz yz
 static std::vector<double> pack_inertia6(const std::vector<double>& f9) {
   const size_t nb = f9.size() / 9;
   std::vector<double> i6(6 * nb);
-  for (size_t b = 0; b < nb; b++) {
-    const double* s = &f9[9 * b];
-    double* o = &i6[6 * b];
-    o[0] = s[0], o[1] = s[4], o[2] = s[8], o[3] = s[1], o[4] = s[2], o[5] = s[5];
-  }
+  for (size_t b = 0; b < nb; b++) vnl_pack_inertia6(&f9[9 * b], &i6[6 * b]);
   return i6;
 }
-static double total_mass_inv_of(const std::vector<double>& mass) {
-  double tm = 0;
-  for (double x : mass) tm += x;
-  return 1.0 / tm;
-}
+static double total_mass_inv_of(const std::vector<double>& mass) { return vnl_total_mass_inv(mass.data(), (int)mass.size()); }
 static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm) {
   const int nb = (int)in.scalar("nbody");
   const auto& bp = in.i.at("body_parentid");
@@ -290,6 +272,13 @@ static bool fuse_welded_bodies(const vnl_model& in, vnl_model* out, FuseMap* fm)
       for (int c = 0; c < 3; c++) fp[c] = fm->out_pos[3 * (size_t)p + c] + t[c];
       qmul_d(&fm->out_quat[4 * (size_t)p], &bquat[4 * (size_t)b], fq);
     }
+  }
+  fm->R_out.assign(9 * (size_t)nb, 0.0), fm->mem_start.assign((size_t)nd + 1, 0), fm->mem.assign(nb, 0);
+  for (int b = 0; b < nb; b++) qmat_d(&fm->out_quat[4 * (size_t)b], &fm->R_out[9 * (size_t)b]), fm->mem_start[fm->out_dyn[b] + 1]++;
+  for (int k = 0; k < nd; k++) fm->mem_start[k + 1] += fm->mem_start[k];
+  {
+    std::vector<int> at(fm->mem_start.begin(), fm->mem_start.end() - 1);
+    for (int b = 0; b < nb; b++) fm->mem[at[fm->out_dyn[b]]++] = b;
   }
   if (nd == nb) return false;
   *out = in;
@@ -397,6 +386,8 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
       return fail(VNL_ERR_BLOB, "blob section %s missing or of unexpected size", "body_ipos / body_inertia_full");
     if (hm->has_f("body_inertia", 3 * nbo) && hm->has_f("body_iquat", 4 * nbo))
       env->inertia0 = hm->f.at("body_inertia"), env->iquat0 = hm->f.at("body_iquat");
+    env->R_iq0.assign(env->iquat0.empty() ? 0 : 9 * nbo, 0.0);
+    for (size_t b = 0; b < env->R_iq0.size() / 9; b++) qmat_d(&env->iquat0[4 * b], &env->R_iq0[9 * b]);
   }
   if (fuse_welded_bodies(*hm, &fused, &fmap)) hm = &fused;
   d.nbody_out = fmap.nb_out;
@@ -1291,18 +1282,9 @@ static const char* body_row(const vnl_env* env, const double* mass, const double
   std::vector<double> full;
   if (inertia) {  // compiled full inertia + R diag(moments - compiled moments) R': exactly the compiled one where they are equal
     full = env->ifull0;
-    for (int b = 1; b < nb; b++) {
-      double dl[3], R[9];
-      for (int k = 0; k < 3; k++) dl[k] = inertia[3 * (size_t)b + k] - env->inertia0[3 * (size_t)b + k];
-      if (dl[0] == 0 && dl[1] == 0 && dl[2] == 0) continue;
-      qmat_d(&env->iquat0[4 * (size_t)b], R);
-      for (int r = 0; r < 3; r++)
-        for (int q = 0; q < 3; q++) {
-          double v = 0;
-          for (int a = 0; a < 3; a++) v += R[3 * r + a] * dl[a] * R[3 * q + a];
-          full[9 * (size_t)b + 3 * r + q] += v;
-        }
-    }
+    for (int b = 1; b < nb; b++)
+      vnl_full_inertia(&env->ifull0[9 * (size_t)b], &env->R_iq0[9 * (size_t)b], &inertia[3 * (size_t)b], &env->inertia0[3 * (size_t)b],
+                       &full[9 * (size_t)b]);
   }
   std::vector<double> M, nip, nI;
   fuse_inertial(*env->fmap, nd, mass ? mass : env->mass0.data(), ipos ? ipos : env->ipos0.data(),
@@ -1371,12 +1353,26 @@ static int domain_tables(vnl_env* env) {
   return VNL_OK;
 }
 
+// DevDomainRanges::on: which of the two range sets the env has (one word, read by every reset env of a randomised kernel)
+static int ranges_on(const vnl_env* env) {
+  return (env->has_ranges ? VNL_RANGES_FOUR : 0) | (env->has_body_ranges ? VNL_RANGES_BODY : 0);
+}
 static int clear_domain_ranges(vnl_env* env) {
   if (env->has_ranges) {
-    const DevDomainRanges none{};
+    env->has_ranges = 0;
+    DevDomainRanges none{};
+    none.on = ranges_on(env);
     HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, rng), &none, sizeof(DevDomainRanges), hipMemcpyHostToDevice));
   }
   env->has_ranges = 0;
+  return VNL_OK;
+}
+static int clear_body_ranges(vnl_env* env) {
+  if (env->has_body_ranges) {
+    env->has_body_ranges = 0;
+    const int on = ranges_on(env);
+    HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, rng) + offsetof(DevDomainRanges, on), &on, sizeof(int), hipMemcpyHostToDevice));
+  }
   return VNL_OK;
 }
 
@@ -1496,7 +1492,8 @@ extern "C" int vnl_env_set_domain_ranges(vnl_env* env, const vnl_domain_ranges* 
   HIPCHK(hipMemcpy(env->rng_buf, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
   const size_t B = (size_t)env->B;
   DevDomainRanges dr{};
-  dr.on = 1, dr.shared = rg->shared, dr.cg_t = env->rng_buf;
+  env->has_ranges = 1;
+  dr.on = ranges_on(env), dr.shared = rg->shared, dr.cg_t = env->rng_buf;
   for (int f = 0; f < 4; f++)
     if (at[f]) dr.lo[f] = env->rng_buf + at[f], dr.hi[f] = env->rng_buf + at[f] + fields[f].n;
   dr.cg_mu = env->dom, dr.cg_invweight = env->dom + B * d.ncg, dr.act_gain = env->dom + 2 * B * d.ncg;  // (the layout of domain_tables)
@@ -1509,7 +1506,8 @@ extern "C" int vnl_env_set_domain_ranges(vnl_env* env, const vnl_domain_ranges* 
 // The redraw of vnl_env_reset_done as a launch of its own (EnvWaveT::redraw_domain; include/vnl.h)
 extern "C" int vnl_env_redraw_domain(vnl_env* env, const float* mask, const vnl_reset_noise* noise, int32_t initial, void* stream) {
   if (!env || !noise) return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: null argument");
-  if (!env->has_ranges) return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: the env has no ranges (vnl_env_set_domain_ranges)");
+  if (!env->has_ranges && !env->has_body_ranges)
+    return fail(VNL_ERR_ARG, "vnl_env_redraw_domain: the env has no ranges (vnl_env_set_domain_ranges, vnl_env_set_body_domain_ranges)");
   if (!noise->step_base) return fail(VNL_ERR_ARG, "vnl_reset_noise: step_base is null (a device pointer to the step counter)");
   if (noise->step_offset < 0 || noise->env_offset < 0)
     return fail(VNL_ERR_ARG, "vnl_reset_noise: step_offset and env_offset must not be negative");
@@ -1521,6 +1519,41 @@ extern "C" int vnl_env_redraw_domain(vnl_env* env, const float* mask, const vnl_
   HIPCHK((hipError_t)vnl_domain_redraw_(env->kc, env->spec, env->B, stream, mask, noise->step_base, noise->step_offset,
                                         (uint32_t)noise->seed, (uint32_t)(noise->seed >> 32), (uint32_t)noise->env_offset, initial));
   return VNL_OK;
+}
+
+// The device buffer of vnl_env_set_body_domain_ranges: float64 sections, then the integer ones (offsets in bytes)
+struct BodyRangesLayout {
+  size_t lo[3], hi[3], raw, out_pos, R_out, ifull0, inertia0, R_iq0, stage, mem_start, mem, body_out, total;
+};
+static BodyRangesLayout body_ranges_layout(const vnl_env* env) {
+  const size_t B = (size_t)env->B, nb = (size_t)env->dm.nbody_out, nd = (size_t)env->dm.nbody, w[3] = {1, 3, 3};
+  BodyRangesLayout L{};
+  size_t o = 0;
+  auto sec = [&o](size_t n, size_t size) {
+    const size_t at = o;
+    o += n * size;
+    return at;
+  };
+  for (int f = 0; f < 3; f++) L.lo[f] = sec(w[f] * nb, 8), L.hi[f] = sec(w[f] * nb, 8);
+  L.raw = sec(B * 7 * nb, 8), L.out_pos = sec(3 * nb, 8), L.R_out = sec(9 * nb, 8), L.ifull0 = sec(9 * nb, 8);
+  L.inertia0 = sec(3 * nb, 8), L.R_iq0 = sec(9 * nb, 8), L.stage = sec(B * (VNL_FOLD_REC * nb + nd), 8);
+  L.mem_start = sec(nd + 1, 4), L.mem = sec(nb, 4), L.body_out = sec(nd, 4);
+  L.total = o;
+  return L;
+}
+// [B][7 nb] mass | moments | ipos of every env: what vnl_env_set_body_domain was given, else the compiled values (moments of a
+// model without body_inertia: zeros, as its compiled moments read -- the difference the full inertia is built from is zero)
+static std::vector<double> body_raw_rows(const vnl_env* env) {
+  const size_t B = (size_t)env->B, nb = (size_t)env->dm.nbody_out, w[3] = {1, 3, 3}, at[3] = {0, nb, 4 * nb};
+  const std::vector<double> zeros(3 * nb, 0.0);
+  const std::vector<double>* model[3] = {&env->mass0, env->inertia0.empty() ? &zeros : &env->inertia0, &env->ipos0};
+  std::vector<double> raw(B * 7 * nb);
+  for (size_t e = 0; e < B; e++)
+    for (int f = 0; f < 3; f++) {
+      const double* src = env->body_raw[f].empty() ? model[f]->data() : &env->body_raw[f][e * w[f] * nb];
+      std::copy(src, src + w[f] * nb, raw.begin() + e * 7 * nb + at[f]);
+    }
+  return raw;
 }
 
 extern "C" int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* bd, void* stream) {
@@ -1540,7 +1573,8 @@ extern "C" int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* bd, 
       HIPCHK(hipMemcpy(env->dom + n4, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
     }
     env->has_body = 0, env->has_dom = env->has_dom4;
-    return VNL_OK;
+    for (auto& r : env->body_raw) r.clear();
+    return clear_body_ranges(env);  // (ranges without a body domain would redraw tables nobody owns)
   }
   if (bd->body_inertia && env->inertia0.empty())
     return fail(VNL_ERR_BLOB, "vnl_env_set_body_domain: body_inertia needs the model's body_inertia and body_iquat sections");
@@ -1585,6 +1619,130 @@ extern "C" int vnl_env_set_body_domain(vnl_env* env, const vnl_body_domain* bd, 
   if (rc != VNL_OK) return rc;
   HIPCHK(hipMemcpy(env->dom + n4, tab.data(), tab.size() * sizeof(vreal), hipMemcpyHostToDevice));
   env->has_body = 1, env->has_dom = 1;
+  for (int f = 0; f < 3; f++) env->body_raw[f] = v[f];
+  if (env->brng_buf) {  // (a field without bounds takes these values at a redraw)
+    const std::vector<double> raw = body_raw_rows(env);
+    HIPCHK(hipMemcpy(env->brng_buf + body_ranges_layout(env).raw, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return VNL_OK;
+}
+
+// Ranges of the body-domain redraw at fresh resets (include/vnl.h: vnl_body_domain_ranges).  The contract of
+// vnl_env_set_domain_ranges: waits for `stream`, reads the bounds to the host, validates, and only then allocates and writes.
+extern "C" int vnl_env_set_body_domain_ranges(vnl_env* env, const vnl_body_domain_ranges* rg, void* stream) {
+  if (!env) return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: null env");
+  DeviceGuard guard(env->device);
+  if (!guard.ok) return fail(VNL_ERR_HIP, "hipSetDevice failed");
+#ifndef VNL_FORKJOIN_DEFINED
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+#else
+  (void)stream;
+#endif
+  if (!rg) return clear_body_ranges(env);
+  const DevModel& d = env->dm;
+  const size_t B = (size_t)env->B, nb = (size_t)d.nbody_out, nd = (size_t)d.nbody, n4 = B * (2 * d.ncg + d.nu + 2 * d.nv);
+  const FuseMap& fm = *env->fmap;
+  const struct {
+    const char* name;
+    size_t w;
+    bool nonneg;
+    const std::vector<double>& model;
+  } fields[3] = {{"body_mass", 1, true, env->mass0}, {"body_inertia", 3, true, env->inertia0}, {"body_ipos", 3, false, env->ipos0}};
+  if (rg->shared & ~0x7u) return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: shared has bits beyond the three fields");
+  if (rg->flags & ~VNL_BODY_RANGES_INERTIA_WITH_MASS) return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: unknown flags");
+  for (int f = 0; f < 3; f++)
+    if (!rg->lo[f] != !rg->hi[f])
+      return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: %s: lo and hi must both be given or both be null", fields[f].name);
+  if ((rg->flags & VNL_BODY_RANGES_INERTIA_WITH_MASS) && !rg->lo[0])
+    return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: INERTIA_WITH_MASS needs ranges for body_mass");
+  if (rg->lo[1] && env->inertia0.empty())
+    return fail(VNL_ERR_BLOB, "vnl_env_set_body_domain_ranges: body_inertia needs the model's body_inertia and body_iquat sections");
+  std::vector<double> lo[3], hi[3];
+  for (int f = 0; f < 3; f++) {
+    const auto& F = fields[f];
+    if (!rg->lo[f]) continue;
+    const size_t n = F.w * nb;
+    lo[f].resize(n), hi[f].resize(n);
+    HIPCHK(hipMemcpy(lo[f].data(), rg->lo[f], n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hi[f].data(), rg->hi[f], n * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < F.w; k++) lo[f][k] = hi[f][k] = F.model[k];  // row 0 is not read: never drawn
+    for (size_t k = 0; k < n; k++)
+      if (!(std::isfinite(lo[f][k]) && std::isfinite(hi[f][k]) && lo[f][k] <= hi[f][k] && (!F.nonneg || lo[f][k] >= 0))) {
+        char where[96];
+        snprintf(where, sizeof(where), "index %zu (lo %g, hi %g)", k, lo[f][k], hi[f][k]);
+        return fail(VNL_ERR_ARG, F.nonneg ? "vnl_env_set_body_domain_ranges: %s needs finite 0 <= lo <= hi: %s"
+                                          : "vnl_env_set_body_domain_ranges: %s needs finite lo <= hi: %s", F.name, where);
+      }
+  }
+  // The sufficient condition for what the kernel stores (it does not validate): at the LOWER bounds -- a field without bounds:
+  // the values it keeps -- every dynamic body that carries dofs has a member mass sum > 0 and a member with three moments > 0,
+  // and the total mass is > 0 (include/vnl.h has the reasoning).
+  const std::vector<double> raw = body_raw_rows(env);
+  const bool per_env = !env->body_raw[0].empty() || !env->body_raw[1].empty() || !env->body_raw[2].empty();
+  for (size_t e = 0; e < (per_env ? B : 1); e++) {
+    const double *m = lo[0].empty() ? &raw[e * 7 * nb] : lo[0].data(), *mom = lo[1].empty() ? &raw[e * 7 * nb + nb] : lo[1].data();
+    double tm = 0;
+    for (size_t dyn = 0; dyn < nd; dyn++) {
+      double M = 0;
+      bool solid = env->inertia0.empty();
+      for (int i = fm.mem_start[dyn]; i < fm.mem_start[dyn + 1]; i++) {
+        const size_t b = (size_t)fm.mem[i];
+        M += m[b], solid = solid || (mom[3 * b] > 0 && mom[3 * b + 1] > 0 && mom[3 * b + 2] > 0);
+      }
+      tm += M;
+      if (dyn == 0 || env->dyn_dofnum[dyn] <= 0) continue;
+      char why[200];
+      if (!(M > 0)) {
+        snprintf(why, sizeof(why), "dynamic body %zu (body %d as given, with what is welded to it) carries dofs and has mass %g", dyn,
+                 fm.body_out[dyn], M);
+        return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: body_mass: at the lower bounds %s", why);
+      }
+      if (!solid) {
+        snprintf(why, sizeof(why), "no member of dynamic body %zu (body %d as given) has three moments > 0", dyn, fm.body_out[dyn]);
+        return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: body_inertia: at the lower bounds %s", why);
+      }
+    }
+    if (!(tm > 0)) {
+      char why[64];
+      snprintf(why, sizeof(why), "total mass %g", tm);
+      return fail(VNL_ERR_ARG, "vnl_env_set_body_domain_ranges: body_mass: at the lower bounds %s", why);
+    }
+  }
+  int rc = domain_tables(env);  // (an env without a domain: the tables at the compiled values)
+  if (rc != VNL_OK) return rc;
+  const BodyRangesLayout L = body_ranges_layout(env);
+  if (!env->brng_buf) {  // room for every field, whatever this call gives
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, L.total));
+    env->allocs.push_back(p);
+    env->brng_buf = (char*)p;
+  }
+  std::vector<char> buf(L.stage);  // (everything in front of the staging area, which needs no initial value)
+  auto put = [&buf](size_t at, const std::vector<double>& src) {
+    if (!src.empty()) memcpy(buf.data() + at, src.data(), src.size() * sizeof(double));
+  };
+  for (int f = 0; f < 3; f++) put(L.lo[f], lo[f]), put(L.hi[f], hi[f]);
+  put(L.raw, raw), put(L.out_pos, fm.out_pos), put(L.R_out, fm.R_out), put(L.ifull0, env->ifull0);
+  put(L.inertia0, env->inertia0), put(L.R_iq0, env->R_iq0);  // (absent: zeros, see body_raw_rows)
+  HIPCHK(hipMemcpy(env->brng_buf, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(env->brng_buf + L.mem_start, fm.mem_start.data(), (nd + 1) * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(env->brng_buf + L.mem, fm.mem.data(), nb * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(env->brng_buf + L.body_out, fm.body_out.data(), nd * sizeof(int), hipMemcpyHostToDevice));
+  DevBodyRanges br{};
+  auto D = [&](size_t at) { return (double*)(env->brng_buf + at); };
+  br.shared = rg->shared, br.flags = rg->flags;
+  for (int f = 0; f < 3; f++)
+    if (!lo[f].empty()) br.lo[f] = D(L.lo[f]), br.hi[f] = D(L.hi[f]);
+  br.raw = D(L.raw), br.out_pos = D(L.out_pos), br.R_out = D(L.R_out), br.ifull0 = D(L.ifull0), br.inertia0 = D(L.inertia0);
+  br.R_iq0 = D(L.R_iq0), br.stage = D(L.stage);
+  br.mem_start = (const int*)(env->brng_buf + L.mem_start), br.mem = (const int*)(env->brng_buf + L.mem);
+  br.body_out = (const int*)(env->brng_buf + L.body_out);
+  br.body_mass = env->dom + n4, br.body_ipos = br.body_mass + B * nd, br.body_inertia6 = br.body_mass + 4 * B * nd;  // (domain_tables)
+  br.total_mass_inv = br.body_mass + 10 * B * nd;
+  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, brng), &br, sizeof(DevBodyRanges), hipMemcpyHostToDevice));
+  env->has_body_ranges = 1, env->has_body = 1, env->has_dom = 1;
+  const int on = ranges_on(env);
+  HIPCHK(hipMemcpy((char*)env->kc + offsetof(KernelConsts, rng) + offsetof(DevDomainRanges, on), &on, sizeof(int), hipMemcpyHostToDevice));
   return VNL_OK;
 }
 

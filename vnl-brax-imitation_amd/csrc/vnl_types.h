@@ -300,14 +300,34 @@ struct DevDomain {
 
 /* Ranges of the domain redraw at fresh resets (vnl_env_set_domain_ranges; EnvWaveT::redraw_domain), library-owned device
  * memory.  Fields in the order of vnl_domain: cg_friction, act_gain, dof_damping, dof_armature. */
+#define VNL_RANGES_FOUR 1 /* bits of DevDomainRanges::on */
+#define VNL_RANGES_BODY 2
 struct DevDomainRanges {
-  int on;          /* 0: no ranges, nothing below is read */
+  int on;          /* 0: no ranges; VNL_RANGES_FOUR: the fields below are set; VNL_RANGES_BODY: KernelConsts::brng is (one word
+                      for both, so that a reset env reads one word of the constant block before its draws) */
   uint32_t shared; /* bit f: one uniform per (env, episode) for the whole field f */
   const double *lo[4], *hi[4]; /* [n_f] absolute bounds per element; both null: field f is never redrawn */
   const double* cg_t;          /* [ncg] what the contact rows' inverse weight is derived from, then impratio at [ncg] */
   /* WRITABLE views of the five tables DevDomain points at (the same allocation): the redraw stores through these, the
      kernels go on reading through DevDomain */
   vreal *cg_mu, *cg_invweight, *act_gain, *dof_damping, *dof_armature;
+};
+
+/* Ranges of the BODY-domain redraw at fresh resets (vnl_env_set_body_domain_ranges; EnvWaveT::redraw_body_domain), read only
+ * where DevDomainRanges::on has VNL_RANGES_BODY.  Everything points into one library-owned device buffer.  Fields in the order
+ * of vnl_body_domain: body_mass [nb], body_inertia [nb][3], body_ipos [nb][3] over the nb bodies AS GIVEN. */
+struct DevBodyRanges {
+  uint32_t shared; /* bit f: one uniform per (env, episode) for the whole field f */
+  uint32_t flags;  /* VNL_BODY_RANGES_INERTIA_WITH_MASS */
+  const double *lo[3], *hi[3]; /* absolute bounds per element; both null: field f takes this env's row of `raw` */
+  const double* raw;           /* [B][7 nb] mass | moments | ipos of every env as last set by hand (else the compiled values) */
+  /* what the fold needs (csrc/vnl_inertial.h), float64: the fixed transform of every body in its dynamic body's frame (the
+     rotation as a matrix), the compiled full inertia and moments, the rotation matrix of the compiled iquat */
+  const double *out_pos, *R_out, *ifull0, *inertia0, *R_iq0; /* [nb][3], [nb][9], [nb][9], [nb][3], [nb][9] */
+  const int *mem_start, *mem, *body_out; /* members of dynamic body d: mem[mem_start[d] .. mem_start[d + 1]), ascending; [nd] */
+  double* stage; /* [B][VNL_FOLD_REC nb + nd]: this env's records per body as given, then the fused masses (they cross lanes) */
+  /* WRITABLE views of the four body tables DevDomain points at */
+  vreal *body_mass, *body_ipos, *body_inertia6, *total_mass_inv;
 };
 
 /* Everything the env kernels read that does not change between launches, in one device buffer.  The kernels read
@@ -319,5 +339,6 @@ struct KernelConsts {
   WsLayout L;
   DevDomain dom; /* (after L: the offsets of m, ev and L that the unrandomised kernels read stay as they are) */
   DevDomainRanges rng;
+  DevBodyRanges brng; /* (behind rng: no offset an existing kernel reads moves) */
 };
 

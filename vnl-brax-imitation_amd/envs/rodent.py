@@ -76,6 +76,27 @@ def domain_ranges_scaled(sys, friction=(0.5, 1.5), gain=None, damping=None, arma
     return out
 
 
+def body_domain_ranges_scaled(sys, mass=(0.7, 1.3), inertia=None, ipos=None) -> Dict[str, tuple]:
+    """`ranges` for `with_body_domain_ranges`: absolute (lo, hi) float64 arrays over the bodies of `sys` (a CompiledModel) as
+    given.  `mass`: multiples (lo, hi) of the compiled masses; `inertia`: multiples of the compiled principal moments, None =
+    the mass multiples (with `inertia_with_mass=True` a body then scales like a change of density); `ipos`: (lo, hi) offsets
+    in units of each body's |ipos|, added to every component, None = the centre of mass is not redrawn.  A `mass` of None
+    leaves mass (and, with `inertia` None, the moments) out."""
+    m0 = np.asarray(sys.body_mass, np.float64).reshape(-1)
+    i0 = np.asarray(sys.body_inertia, np.float64).reshape(-1, 3)
+    p0 = np.asarray(sys.body_ipos, np.float64).reshape(-1, 3)
+    out = {}
+    if mass is not None:
+        out["body_mass"] = (m0 * float(mass[0]), m0 * float(mass[1]))
+    inertia = mass if inertia is None else inertia
+    if inertia is not None:
+        out["body_inertia"] = (i0 * float(inertia[0]), i0 * float(inertia[1]))
+    if ipos is not None:
+        r = np.linalg.norm(p0, axis=1, keepdims=True)
+        out["body_ipos"] = (p0 + float(ipos[0]) * r, p0 + float(ipos[1]) * r)
+    return out
+
+
 def _clamped_take(x: np.ndarray, idx: Sequence[int], axis: int) -> np.ndarray:
     """x[..., idx, ...] with JAX's clamp-out-of-range gather semantics."""
     idx = np.clip(np.asarray(idx, dtype=np.int64), 0, x.shape[axis] - 1)
@@ -216,6 +237,8 @@ class RodentTracking(Env):
         new._build(self._build_args[0], int(num_envs), *self._build_args[1:])
         if self._domain_ranges is not None:  # (the ranges, not the tables: the new env's tables hold the compiled values)
             new._set_domain_ranges(self._domain_ranges)
+        if self._body_domain_ranges is not None:
+            new._set_body_domain_ranges(self._body_domain_ranges)
         return new
 
     _domain = None  # {field: (num_envs, n) float64 tensor} of a randomised env (with_domain), else None
@@ -236,9 +259,29 @@ class RodentTracking(Env):
         _lib.check(self._L, self._L.vnl_env_set_domain_ranges(self._env_h, C.byref(desc), self._stream()))
         self._domain_ranges = ({k: tuple(t.clone() for t in v) for k, v in bounds.items()}, tuple(shared))
 
-    def _with_domains(self, tables, body_tables, ranges="carry") -> "RodentTracking":
+    # ({field: (lo, hi) float64 (nbody[, 3]) CPU tensors}, shared field names, inertia_with_mass) of with_body_domain_ranges
+    _body_domain_ranges = None
+
+    def _set_body_domain_ranges(self, ranges) -> None:
+        """vnl_env_set_body_domain_ranges of already shaped ranges (the library validates and copies them: synchronous)"""
+        bounds, shared, with_mass = ranges
+        desc, keep = _lib.BodyDomainRanges(), []
+        for f, k in enumerate(BODY_DOMAIN_FIELDS):
+            if k in bounds:
+                lo, hi = (t.to(self.device).contiguous() for t in bounds[k])
+                keep += [lo, hi]
+                desc.lo[f], desc.hi[f] = lo.data_ptr(), hi.data_ptr()
+                desc.shared |= (1 << f) if k in shared else 0
+        desc.flags = _lib.BODY_RANGES_INERTIA_WITH_MASS if with_mass else 0
+        rc = self._L.vnl_env_set_body_domain_ranges(self._env_h, C.byref(desc), self._stream())
+        if rc == -1:  # VNL_ERR_ARG: what the library checks (bad bounds, a jointed body without mass at the lower bounds, ...)
+            raise ValueError(self._L.vnl_last_error().decode())
+        _lib.check(self._L, rc)
+        self._body_domain_ranges = ({k: tuple(t.clone() for t in v) for k, v in bounds.items()}, tuple(shared), bool(with_mass))
+
+    def _with_domains(self, tables, body_tables, ranges="carry", body_ranges="carry") -> "RodentTracking":
         """A new env of this configuration and num_envs with the given parts of a domain (already validated; None: unset);
-        the ranges of this env are carried over unless others are given."""
+        the ranges of this env (both sets) are carried over unless others are given."""
         new = object.__new__(type(self))
         new.__dict__.update(self._config_attrs)
         new._build(self._build_args[0], self.num_envs, *self._build_args[1:])
@@ -256,7 +299,68 @@ class RodentTracking(Env):
         ranges = self._domain_ranges if isinstance(ranges, str) else ranges
         if ranges is not None:
             new._set_domain_ranges(ranges)
+        body_ranges = self._body_domain_ranges if isinstance(body_ranges, str) else body_ranges
+        if body_ranges is not None:
+            new._set_body_domain_ranges(body_ranges)
         return new
+
+    def with_body_domain_ranges(self, ranges: Mapping[str, Any], shared: Sequence[str] = (),
+                                inertia_with_mass: bool = False) -> "RodentTracking":
+        """A NEW env of the same model, clip, parameters and num_envs whose envs get a new BODY domain per EPISODE
+        (include/vnl.h: vnl_env_set_body_domain_ranges): `reset_done` -- the fresh auto-reset -- draws mass, principal moments
+        and centre of mass of every env it resets anew inside the reset kernel and folds the welded bodies there, and
+        `redraw_domain` does so on request (the first episode).
+
+          ranges  {field: (lo, hi)} with the field names of `with_body_domain`; lo / hi are scalars or arrays of shape
+                  (nbody,) / (nbody, 3): ABSOLUTE bounds per element (`body_domain_ranges_scaled` builds them).  Row 0, the
+                  world body, is never drawn: its bounds are replaced by the compiled values
+          shared  names of fields of `ranges` that take ONE uniform per (env, episode) for all their elements
+          inertia_with_mass  moment (b, k) takes the uniform of body b's mass draw (needs mass ranges): with bounds that are the
+                  same multiples of the compiled values a body scales like a change of density and stays physical; the
+                  moments' triangle inequality is not checked otherwise
+
+        A field left out is never redrawn: it keeps the `with_body_domain` values of this env, else the compiled ones.  Carried
+        by `with_domain` / `with_body_domain` / `with_domain_ranges` / `with_num_envs` exactly as the four-field ranges are.
+        Raises ValueError on an unknown field, a wrong shape, or what the library refuses: non-finite bounds, lo > hi, a mass
+        or moment lo < 0, the flag without mass ranges, or lower bounds that leave a body with dofs without mass or without a
+        member of three positive moments, or a total mass of zero."""
+        nbody, bounds = int(self.dims.nbody), {}
+        compiled = {"body_mass": self.sys.body_mass, "body_inertia": self.sys.body_inertia, "body_ipos": self.sys.body_ipos}
+        for k, v in dict(ranges).items():
+            if k not in BODY_DOMAIN_FIELDS:
+                raise ValueError(f"unknown body domain field {k!r}: expected some of {sorted(BODY_DOMAIN_FIELDS)}")
+            shape = (nbody,) + BODY_DOMAIN_FIELDS[k][0]
+            try:
+                lo, hi = v
+            except (TypeError, ValueError):
+                raise ValueError(f"body domain range {k!r} must be a (lo, hi) pair") from None
+            pair = []
+            for name, x in (("lo", lo), ("hi", hi)):
+                t = torch.as_tensor(x).detach().to(dtype=torch.float64, device="cpu")
+                if t.dim() == 0:
+                    t = t.expand(shape)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"body domain range {k!r}: {name} must be a scalar or have shape {shape}, got {tuple(t.shape)}")
+                t = t.contiguous().clone()
+                t[0] = torch.as_tensor(np.asarray(compiled[k], np.float64).reshape(shape)[0])
+                pair.append(t)
+            bounds[k] = tuple(pair)
+        shared = tuple(shared)
+        for k in shared:
+            if k not in bounds:
+                raise ValueError(f"shared field {k!r} has no range")
+        if inertia_with_mass and "body_mass" not in bounds:
+            raise ValueError("inertia_with_mass needs a range for 'body_mass'")
+        return self._with_domains(self._domain, self._body_domain, body_ranges=(bounds, shared, bool(inertia_with_mass)))
+
+    @property
+    def body_domain_ranges(self) -> Optional[Dict[str, Any]]:
+        """{field: (lo, hi) float64 (nbody[, 3]) tensors} of `with_body_domain_ranges` plus "shared": the shared field names
+        and "inertia_with_mass"; or None."""
+        if self._body_domain_ranges is None:
+            return None
+        bounds, shared, with_mass = self._body_domain_ranges
+        return dict({k: tuple(t.clone() for t in v) for k, v in bounds.items()}, shared=tuple(shared), inertia_with_mass=with_mass)
 
     def with_domain_ranges(self, ranges: Mapping[str, Any], shared: Sequence[str] = ()) -> "RodentTracking":
         """A NEW env of the same model, clip, parameters and num_envs whose envs get a new physical domain per EPISODE
@@ -269,7 +373,7 @@ class RodentTracking(Env):
                   friction scaled alike), instead of one per element
 
         A field left out is never redrawn.  Domains of this env (with_domain, with_body_domain) are carried over: the tables
-        keep those values until an env's first redraw; the body domain is never redrawn.  `with_domain` /
+        keep those values until an env's first redraw; the body domain is redrawn only under `with_body_domain_ranges`.  `with_domain` /
         `with_body_domain` of the result carry the ranges, `with_num_envs` carries the ranges but not the tables.  Raises
         ValueError on an unknown field, a wrong length, or bad bounds (non-finite, lo > hi, friction lo <= 0, damping or
         armature lo < 0)."""
@@ -316,11 +420,12 @@ class RodentTracking(Env):
                       mask: Optional[torch.Tensor] = None, initial: bool = False) -> None:
         """The domain of the envs whose `mask` (B,) is nonzero (None: every env) drawn anew from this env's ranges, in place
         (vnl_env_redraw_domain): the draw `reset_done` makes for the envs it resets, keyed by (seed, step_base[0] +
-        step_offset, env_offset + env index) -- ppo_imitation/philox.py domain_draws -- as a launch of its own.
+        step_offset, env_offset + env index) -- ppo_imitation/philox.py domain_draws, body_domain_draws -- as a launch of its
+        own; both kinds of ranges (with_domain_ranges, with_body_domain_ranges) are drawn, whichever the env has.
         `initial=True` draws from a block range of its own: the domain of a FIRST episode differs from that of a reset at the
         same counter.  `step_base`: int64 [1] on the env's device (only read), or an int.  ValueError without ranges."""
-        if self._domain_ranges is None:
-            raise ValueError("redraw_domain: this env has no domain ranges (with_domain_ranges)")
+        if self._domain_ranges is None and self._body_domain_ranges is None:
+            raise ValueError("redraw_domain: this env has no domain ranges (with_domain_ranges, with_body_domain_ranges)")
         B = self.num_envs
         if not isinstance(step_base, torch.Tensor):
             step_base = torch.tensor([int(step_base)], dtype=torch.int64, device=self.device)
@@ -428,13 +533,13 @@ class RodentTracking(Env):
         return flat.view(self.num_envs, cnt.value)
 
     def _copy_domain_tables(self, saved: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The five four-field tables as one flat tensor on the env's device (they are one allocation, "dom_mu" first), or --
-        given such a tensor -- written back: a caller that runs fresh resets it must not keep (the warm-up of a graph
-        capture) puts a redrawn domain back with this.  Synchronous."""
+        """The five four-field tables and the four body tables as one flat tensor on the env's device (they are one
+        allocation, "dom_mu" first), or -- given such a tensor -- written back: a caller that runs fresh resets it must not
+        keep (the warm-up of a graph capture) puts a redrawn domain, of either kind, back with this.  Synchronous."""
         ptr, cnt = C.c_void_p(), C.c_int32()
         _lib.check(self._L, self._L.vnl_env_scratch(self._env_h, b"dom_mu", C.byref(ptr), C.byref(cnt)))
         d = self.dims
-        total = self.num_envs * (2 * int(d.ngeom_collide) + int(d.nu) + 2 * int(d.nv))
+        total = self.num_envs * (2 * int(d.ngeom_collide) + int(d.nu) + 2 * int(d.nv) + 10 * int(d.nbody_dynamic) + 1)
         flat = saved if saved is not None else torch.empty(total, dtype=self._dtype, device=self.device)
         assert flat.numel() == total and flat.dtype == self._dtype and flat.is_contiguous()
         nbytes = C.c_size_t(flat.element_size() * total)

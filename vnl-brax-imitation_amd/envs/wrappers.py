@@ -92,7 +92,7 @@ class AutoResetWrapper(Wrapper):
     With `start_priority` (envs/start_priority.py StartPriority; mode="fresh" only) start frame and clip are drawn from its
     table and the episodes that end are counted into its counters -- not those an EpisodeWrapper below truncated.  The
     caller runs its `update()` (between unrolls).
-    An env with domain ranges (`with_domain_ranges`; mode="fresh" only has a use for them) gets a new physical domain with
+    An env with domain ranges (`with_domain_ranges`, `with_body_domain_ranges`; mode="fresh" only has a use for them) gets a new physical domain with
     every fresh reset -- the reset kernel reads the ranges from the env, no argument here -- and `reset` draws the domain of
     every env's FIRST episode (`redraw_domain(initial=True)` at this wrapper's seed, the counter's value and env_offset).
     """
@@ -119,7 +119,8 @@ class AutoResetWrapper(Wrapper):
             counter = torch.zeros(1, dtype=torch.int64, device=base.device)
             if reset_step is not None:
                 counter.copy_(torch.as_tensor(reset_step, dtype=torch.int64).reshape(1))
-            if getattr(base, "domain_ranges", None) is not None:  # the first episodes are randomised too: before their reset
+            if (getattr(base, "domain_ranges", None) is not None or
+                    getattr(base, "body_domain_ranges", None) is not None):  # the first episodes are randomised too: before their reset
                 base.redraw_domain(seed=self.seed, step_base=counter, env_offset=self.env_offset, initial=True)
             state = self.env.reset(rng, **kw)
             state.info["reset_step"] = counter
@@ -196,7 +197,8 @@ class EvalWrapper(Wrapper):
 
 def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None,
          reset_info_on_autoreset: bool = False, auto_reset: str = "first_state", auto_reset_seed: int = 0,
-         env_offset: int = 0, start_priority=None, domain_ranges=None, domain_shared=()) -> Wrapper:
+         env_offset: int = 0, start_priority=None, domain_ranges=None, domain_shared=(), body_domain_ranges=None,
+         body_domain_shared=(), body_inertia_with_mass: bool = False) -> Wrapper:
     """brax.envs.training.wrap minus the VmapWrapper (natively batched env).
 
     `randomization_fn(sys) -> {field: (num_envs, n) values}` (brax's contract once its `rng` is bound; train.py binds
@@ -211,7 +213,13 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
 
     `domain_ranges` ({field: (lo, hi)}, `domain_shared`: `env.with_domain_ranges`), with "fresh" only: every fresh reset draws
     the env's physical domain anew inside the reset kernel, and the wrapper's `reset` draws that of the first episodes.
-    Applied after `randomization_fn`, whose values an env keeps until its first redraw."""
+    Applied after `randomization_fn`, whose values an env keeps until its first redraw.  `body_domain_ranges`
+    (`body_domain_shared`, `body_inertia_with_mass`: `env.with_body_domain_ranges`) does the same for body mass, principal
+    moments and centre of mass, under the same rule."""
+    if body_domain_ranges is not None and auto_reset != "fresh":
+        raise ValueError("body_domain_ranges needs auto_reset='fresh': the cached first state belongs to one domain")
+    if body_domain_ranges is None and (tuple(body_domain_shared) or body_inertia_with_mass):
+        raise ValueError("body_domain_shared / body_inertia_with_mass without body_domain_ranges")
     if domain_ranges is not None and auto_reset != "fresh":
         raise ValueError("domain_ranges needs auto_reset='fresh': the cached first state belongs to one domain")
     if domain_ranges is None and tuple(domain_shared):
@@ -231,5 +239,9 @@ def wrap(env: Env, episode_length: int = 1000, action_repeat: int = 1, randomiza
         if not hasattr(env, "with_domain_ranges"):
             raise ValueError(f"{type(env).__name__} has no with_domain_ranges: a domain redraw needs a tracking env of this library")
         env = env.with_domain_ranges(domain_ranges, shared=domain_shared)
+    if body_domain_ranges is not None:
+        if not hasattr(env, "with_body_domain_ranges"):
+            raise ValueError(f"{type(env).__name__} has no with_body_domain_ranges: a domain redraw needs a tracking env of this library")
+        env = env.with_body_domain_ranges(body_domain_ranges, shared=body_domain_shared, inertia_with_mass=body_inertia_with_mass)
     return AutoResetWrapper(EpisodeWrapper(env, episode_length, action_repeat), reset_info_on_autoreset, mode=auto_reset,
                             seed=auto_reset_seed, env_offset=env_offset, start_priority=start_priority)

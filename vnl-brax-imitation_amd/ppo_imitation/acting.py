@@ -230,7 +230,8 @@ class GraphedUnroll:
         saved_counters = [c.clone() for c in counters]
         # (.. nor redraw the domain: with ranges the warm-up's fresh resets write the library-owned tables)
         base = fz[0].unwrapped
-        saved_domain = base._copy_domain_tables() if getattr(base, "domain_ranges", None) is not None else None
+        saved_domain = (base._copy_domain_tables() if getattr(base, "domain_ranges", None) is not None or
+                        getattr(base, "body_domain_ranges", None) is not None else None)
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):

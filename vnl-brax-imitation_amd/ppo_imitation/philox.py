@@ -29,6 +29,7 @@ STREAM_RESET = 3  # the last one: the stream field is the low two bits of counte
 RESET_INT_BLOCK = 0x80000000  # the block of stream 3 whose words x0, x1 give start frame and clip
 DOMAIN_BLOCK, DOMAIN_INITIAL, DOMAIN_FIELD_STRIDE = 0x40000000, 0x20000000, 0x00100000  # stream 3: the domain redraw
 DOMAIN_FIELDS = ("cg_friction", "act_gain", "dof_damping", "dof_armature")  # field index f, the order of vnl_domain
+BODY_DOMAIN_FIELDS = ("body_mass", "body_inertia", "body_ipos")  # field indices 4, 5, 6: the order of vnl_body_domain
 SHARED_ENV = 0xFFFFFFFF  # the env word of stream 2: no env may have this index
 
 IntLike = Union[int, torch.Tensor]
@@ -127,6 +128,45 @@ def domain_draws(seed: int, step: IntLike, env: torch.Tensor, field: IntLike, lo
     w = hi - lo
     p = u.cpu() * w
     return lo + p
+
+
+def body_domain_draws(seed: int, step: IntLike, env: torch.Tensor, ranges, shared=(), inertia_with_mass: bool = False,
+                      initial: bool = False) -> dict:
+    """{field: float64 (len(env), nbody[, 3])}: the values a body-domain redraw (vnl_env_reset_done with body ranges,
+    vnl_env_redraw_domain; include/vnl.h: vnl_body_domain_ranges) draws for the fields of `ranges` ({field: (lo, hi)} float64
+    (nbody,) / (nbody, 3): what RodentTracking.body_domain_ranges returns, further keys ignored) of the envs with GLOBAL indices
+    `env` at `step`.  Field indices 4, 5, 6 of the block range of `domain_draws`, the field flattened: element j takes word
+    j % 4 of block j / 4, a field in `shared` word 0 of block 0; with `inertia_with_mass` moment (b, k) takes the word of body
+    b's mass.  Row 0 (the world body) is never drawn: it holds lo[0], which with_body_domain_ranges sets to the compiled
+    values.  The arithmetic is domain_draws': the bits of the device."""
+    env = torch.as_tensor(env)
+    B, out, u_mass = env.shape[0], {}, None
+    if inertia_with_mass and "body_mass" not in ranges:
+        raise ValueError("inertia_with_mass needs a range for 'body_mass'")
+    for k in BODY_DOMAIN_FIELDS:
+        if k not in ranges:
+            continue
+        f = 4 + BODY_DOMAIN_FIELDS.index(k)
+        lo, hi = (torch.as_tensor(x, dtype=torch.float64).cpu() for x in ranges[k])
+        shape, n = tuple(lo.shape), lo.numel()
+        assert tuple(hi.shape) == shape and n <= 4 * DOMAIN_FIELD_STRIDE
+        lo, hi = lo.reshape(-1), hi.reshape(-1)
+        if k == "body_inertia" and inertia_with_mass:
+            u = u_mass.repeat_interleave(3, dim=1)
+        else:
+            block0 = DOMAIN_BLOCK + (DOMAIN_INITIAL if initial else 0) + f * DOMAIN_FIELD_STRIDE
+            one = k in shared
+            x = _words(seed, step, env, 1 if one else n, STREAM_RESET, block0=block0).reshape(B, -1)
+            x = x[:, :1].expand(B, n) if one else x[:, :n]
+            u = ((x.to(torch.float64) + 0.5) * 2.0 ** -32).cpu()
+        if k == "body_mass":
+            u_mass = u
+        w = hi - lo
+        p = u * w
+        v = (lo + p).reshape((B,) + shape).clone()
+        v[:, 0] = lo.reshape(shape)[0]
+        out[k] = v
+    return out
 
 
 def contact_invweight(t, mu, impratio: float):

@@ -149,6 +149,9 @@ def train(
     start_priority: Any = False,
     domain_ranges=None,
     domain_shared=(),
+    body_domain_ranges=None,
+    body_domain_shared=(),
+    body_inertia_with_mass: bool = False,
 ):
     """PPO training (train.py:62-491).
 
@@ -200,6 +203,8 @@ def train(
     is needed with several ranks.  The evaluator's env gets the ranges and ONE draw, on the eval seed: its later episodes are
     not redrawn, as its auto-reset is not fresh (EvalWrapper scores first episodes only).  A checkpoint does not carry the
     tables: a resumed run resets its envs once more, with the initial draw made at the resumed counter.
+    `body_domain_ranges` (`body_domain_shared`, `body_inertia_with_mass`: envs/rodent.py with_body_domain_ranges /
+    body_domain_ranges_scaled) does the same for body mass, principal moments and centre of mass, under the same rules.
 
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
@@ -237,7 +242,8 @@ def train(
                             randomization_fn=bind_randomization(randomization_fn, local_envs, seed),
                             reset_info_on_autoreset=reset_info_on_autoreset, auto_reset=auto_reset,
                             auto_reset_seed=seed * 2654435761 + 97, env_offset=rank * local_envs, start_priority=prio,
-                            domain_ranges=domain_ranges, domain_shared=domain_shared)
+                            domain_ranges=domain_ranges, domain_shared=domain_shared, body_domain_ranges=body_domain_ranges,
+                            body_domain_shared=body_domain_shared, body_inertia_with_mass=body_inertia_with_mass)
     env_state = env.reset(g_env)
 
     normalize = (lambda x, y: x)
@@ -285,7 +291,7 @@ def train(
             training_state.policy_counter.copy_(ck["policy_counter"])
         if training_state.reset_step is not None and "reset_step" in ck:  # (the episode draws go on, not from step 0 again)
             training_state.reset_step.copy_(ck["reset_step"])
-            if domain_ranges is not None:  # (the tables are not in the checkpoint: the initial draw at the resumed counter)
+            if domain_ranges is not None or body_domain_ranges is not None:  # (the tables are not in the checkpoint: the initial draw at the resumed counter)
                 env_state = env.reset(g_env, reset_step=ck["reset_step"])
                 training_state.reset_step = env_state.info["reset_step"]
         if prio is not None and "start_priority" in ck:
@@ -621,8 +627,13 @@ def train(
         ev_wrapped = env_wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat,
                                        randomization_fn=bind_randomization(randomization_fn, num_eval_envs, seed * 31 + 7),
                                        reset_info_on_autoreset=reset_info_on_autoreset)
-        if domain_ranges is not None:  # one draw on the eval seed; first_state auto-reset keeps it (see the docstring)
-            ev_base = ev_wrapped.unwrapped.with_domain_ranges(domain_ranges, shared=domain_shared)
+        if domain_ranges is not None or body_domain_ranges is not None:  # one draw on the eval seed; first_state auto-reset keeps it (see the docstring)
+            ev_base = ev_wrapped.unwrapped
+            if domain_ranges is not None:
+                ev_base = ev_base.with_domain_ranges(domain_ranges, shared=domain_shared)
+            if body_domain_ranges is not None:
+                ev_base = ev_base.with_body_domain_ranges(body_domain_ranges, shared=body_domain_shared,
+                                                          inertia_with_mass=body_inertia_with_mass)
             ev_base.redraw_domain(seed=seed * 31 + 7, step_base=0, initial=True)
             ev_wrapped = env_wrappers.wrap(ev_base, episode_length=episode_length, action_repeat=action_repeat,
                                            reset_info_on_autoreset=reset_info_on_autoreset)
