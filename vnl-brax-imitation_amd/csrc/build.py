@@ -42,6 +42,12 @@ OUT = os.path.join(HERE, "libvnl.so")
 #          sum and scan a sequence of its own, the last trip of dof_prefix (nine dofs of the rodent's 73) as six full scans
 #          (regression build for vnl_rows_join / VNL_WAVE_SUMS / VNL_SCAN6 and dof_prefix's tail form of csrc/vnl_body.h: the
 #          same adds on the same operands, the same bits on every output; tests/test_gpu_xlane_plain.py)
+#   treeplain -DVNL_TREE_PLAIN: the two subtree sums of a substep (composite inertias, cfrc child into parent) in the
+#          specialised kernels as the generic ones still do them -- a walk that reads the parent bytes from LDS and decides per
+#          body with compares and selects whether it is a chain link, which register of its group of eight is the parent, or
+#          whether the parent lies below the group (regression build for EnvWaveT::tree_accumulate_const of csrc/vnl_body.h,
+#          the walk unrolled over VnlSpecRodent::body_parent: the same adds on the same operands in the same order, the same
+#          bits on every output; tests/test_gpu_tree_const.py)
 #   spill  env kernels compiled under a 128-VGPR cap, which forces ~230 registers per lane to spill to scratch
 #          memory: results must not depend on spilling (tests/test_gpu_spill.py)
 #   nospec -DVNL_NO_SPEC: the generic kernels (dims and LDS offsets read at run time) on the rodent too: the specialised ones
@@ -53,7 +59,8 @@ OUT = os.path.join(HERE, "libvnl.so")
 TWO_WAVES = "-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"
 _DEFINES = {"prof": "VNL_PROFILE", "knobs": "VNL_STAGE_KNOBS", "noblk": "VNL_NO_BLK", "tail": "VNL_SOLVER_TAIL",
             "plain": "VNL_SOLVER_PLAIN", "vmemplain": "VNL_VMEM_PLAIN", "ldsplain": "VNL_LDS_PLAIN",
-            "sgprplain": "VNL_SGPR_PLAIN", "xlaneplain": "VNL_XLANE_PLAIN", "nospec": "VNL_NO_SPEC"}
+            "sgprplain": "VNL_SGPR_PLAIN", "xlaneplain": "VNL_XLANE_PLAIN", "treeplain": "VNL_TREE_PLAIN",
+            "nospec": "VNL_NO_SPEC"}
 VARIANTS = {
     "product": ("libvnl.so", [TWO_WAVES]),
     "spill": ("libvnl_spill.so", ["-DVNL_KERNEL_ATTR=__attribute__((amdgpu_waves_per_eu(4,4)))"]),
@@ -62,7 +69,8 @@ VARIANTS = {
 # What the driver entry builds (__graft_entry__.build): the product and the regression builds the tests load.  A new
 # regression build is a paragraph above, an entry of _DEFINES and a name here; its device test is a few calls into
 # tests/variant_cases.py, its host test (tests/helpers.py HOSTSIM_VARIANTS) into tests/hostsim_cases.py.
-DRIVER_VARIANTS = ("product", "spill", "noblk", "nospec", "tail", "plain", "vmemplain", "ldsplain", "sgprplain", "xlaneplain")
+DRIVER_VARIANTS = ("product", "spill", "noblk", "nospec", "tail", "plain", "vmemplain", "ldsplain", "sgprplain", "xlaneplain",
+                   "treeplain")
 ENV_KERNELS = ("vnl_step_kernel", "vnl_reset_kernel", "vnl_reset_done_kernel")
 
 

@@ -30,6 +30,7 @@
 //     the factor (L' D L).
 #pragma once
 #include <math.h>
+#include <utility>
 #ifdef VNL_FORKJOIN_DEFINED /* the host simulation: blk_apply asserts what its phase form relies on */
 #include <assert.h>
 #endif
@@ -882,11 +883,68 @@ struct EnvWaveT {
   // directly follows its parent in the numbering (a chain link: most links of a depth-first numbering) hands its
   // sum over in a REGISTER; only a child at a branching point adds into its parent through LDS.  (The plain form
   // `s[parent] += s[b]` made every one of the ~64 steps a dependent LDS read-modify-write.)
+  //
+  // A specialised kernel knows the tree (SP::body_parent): the same adds on the same operands in the same order with every
+  // index a constant -- no parent bytes, no compares, no selects, no branch; one burst of LDS reads, one add per body
+  // (two at a child of a branching point), one burst of writes.  -DVNL_TREE_PLAIN (csrc/build.py --treeplain) keeps the
+  // run-time walk in the specialised kernels too.
   VNL_HD void tree_accumulate(int base, int width) const {
+#ifndef VNL_TREE_PLAIN
+    if constexpr (SP::fixed) {
+      tree_accumulate_const(base, width, std::make_integer_sequence<int, SP::D.nbody - 1>{});
+      return;
+    }
+#endif
+    tree_accumulate_walk(base, width);
+  }
+  static constexpr int TREE_G = 8;  // bodies per trip of the run-time walk (a power of two): both forms below read it
+  // Does the run-time walk below add body c into its parent through LDS (true), or in a register of the parent's group of
+  // TREE_G (false)?  The bodies above the highest full group always go through LDS.
+  static constexpr bool tree_adds_through_lds(int c) {
+    constexpr int G = TREE_G, n = SP::D.nbody, top = ((n - 1) & (G - 1)) == G - 1 ? n - 1 : ((n - 1) & ~(G - 1)) - 1;
+    return c > top || (int)SP::body_parent[c] < (c & ~(G - 1));
+  }
+  // Body B's value in memory was already rewritten before the walk reads it: a branching child was added into it through LDS
+  static constexpr bool tree_rewritten(int B) {
+    for (int c = B + 2; c < SP::D.nbody; c++)
+      if ((int)SP::body_parent[c] == B && tree_adds_through_lds(c)) return true;
+    return false;
+  }
+  // One body of the walk: v = x[B] + carry, carry the chain child's v or the literal zero (which IEEE addition keeps: it
+  // turns a -0.0 into +0.0 before the value reaches the parent); a branching child adds its v into its parent's x.
+  static constexpr bool tree_chain_child(int b) { return b + 1 < SP::D.nbody && (int)SP::body_parent[b + 1] == b; }
+  template <int B, int N>
+  VNL_HD static void tree_body(vreal (&x)[N], vreal (&v)[N]) {
+    constexpr int p = (int)SP::body_parent[B];
+    if constexpr (tree_chain_child(B)) v[B] = x[B] + v[B + 1];
+    else v[B] = x[B] + vreal(0.);
+    if constexpr (p != B - 1 && p > 0) x[p] += v[B];
+  }
+  // A value is written back where it differs from what the run-time walk would have read: from the value as loaded, or --
+  // where LDS adds had already rewritten it -- in any case (v then has the bits of what that walk leaves: no sum is -0.0).
+  template <int B, int N>
+  VNL_HD void tree_store(int o, int width, const vreal (&x0)[N], const vreal (&v)[N]) const {
+    constexpr bool always = tree_rewritten(B);
+    if (always || v[B] != x0[B]) s[o + width * B] = v[B];
+  }
+  template <int... I>
+  VNL_HD void tree_accumulate_const(int base, int width, std::integer_sequence<int, I...>) const {
+    constexpr int N = SP::D.nbody;
+    VNL_FOR(k, width) {
+      const int o = base + k;
+      vreal x[N], x0[N], v[N];
+      x[0] = x0[0] = v[0] = vreal(0.);  // (the world body takes no part)
+      ((x0[I + 1] = x[I + 1] = s[o + width * (I + 1)]), ...);
+      (tree_body<N - 1 - I, N>(x, v), ...);  // bodies N - 1 .. 1
+      (tree_store<I + 1, N>(o, width, x0, v), ...);
+    }
+    VNL_SYNC();
+  }
+  VNL_HD void tree_accumulate_walk(int base, int width) const {
     VNL_FOR(k, width) {
       vreal carry = vreal(0.);
       int b = MI(nbody) - 1;
-      constexpr int G = 8;  // bodies per trip
+      constexpr int G = TREE_G;  // bodies per trip
       for (; b >= 1 && (b & (G - 1)) != G - 1; b--) {  // down to a group boundary
         const int o = base + width * b + k;
         const vreal v = s[o] + carry;

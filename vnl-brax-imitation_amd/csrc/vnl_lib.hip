@@ -130,6 +130,7 @@ struct vnl_env {
   std::vector<double> mass0, ipos0, ifull0, inertia0, iquat0;  // (inertia0 / iquat0 empty: the blob does not carry them)
   std::vector<double> R_iq0;                                   // [nbody as given][9] rotation matrix of iquat0 (qmat_d), once
   std::vector<int> dyn_dofnum;                                 // dofs of every dynamic body
+  std::vector<int> dyn_parent;                                 // parent of every dynamic body (the fused tree)
   // vnl_env_set_body_domain_ranges: one device buffer (bounds, what the fold needs, per-env raw fields and staging; see
   // body_ranges_layout) and the host copy of the raw fields vnl_env_set_body_domain was given ([B][n] each, empty: compiled)
   char* brng_buf = nullptr;
@@ -393,6 +394,7 @@ static int build_dev_model(vnl_env* env, const vnl_model* hm) {
   d.nbody_out = fmap.nb_out;
   env->fmap = new FuseMap(fmap);
   env->dyn_dofnum = hm->i.at("body_dofnum");
+  env->dyn_parent = hm->i.at("body_parentid");
   auto S = [&](const char* k) { return hm->scalar(k); };
   d.nq = (int)S("nq"), d.nv = (int)S("nv"), d.nu = (int)S("nu"), d.nbody = (int)S("nbody"), d.njnt = (int)S("njnt");
   d.ncg = (int)S("ncg"), d.ncon = (int)S("ncon"), d.nlimit = (int)S("nlimit"), d.nefc = (int)S("nefc");
@@ -941,8 +943,10 @@ extern "C" int vnl_env_create(const vnl_model* hm, const vnl_envspec* es, int32_
     env->rd_start = (int*)(env->rd_noise + (size_t)num_envs * d.nq), env->rd_clip = env->rd_start + num_envs;
   }
   layout(env);
-  // a model whose every dimension and LDS offset equals the compile-time constants of a specialised kernel runs that kernel
-  env->spec = (same_dims(dims_of(env->dm), VnlSpecRodent::D) && same_layout(env->L, VnlSpecRodent::L)) ? 1 : 0;
+  // a model whose every dimension and LDS offset equals the compile-time constants of a specialised kernel, and whose body
+  // tree is the one that kernel's subtree sums are unrolled over, runs that kernel
+  env->spec = (same_dims(dims_of(env->dm), VnlSpecRodent::D) && same_layout(env->L, VnlSpecRodent::L) &&
+               vnl_same_tree<VnlSpecRodent>(env->dyn_parent.data(), (int)env->dyn_parent.size())) ? 1 : 0;
 #ifdef VNL_NO_SPEC
   env->spec = 0;
 #endif

@@ -278,7 +278,23 @@ struct VnlSpecRodent {
                              VNL_ROUTE_ROWS36X2 | (VNL_ROUTE_ROWS36X2 << VNL_ROUTE_QM_INVERSE) | (2 << VNL_ROUTE_PAIR), 0,
                              2 | (2 << 4) | (2 << 8) | (3 << 12), 2, 66};
   static constexpr WsLayout L = vnl_make_layout(D);
+  /* The tree, too: the parent of every dynamic body (body 0 is the world), as the packaged rodent's first nbody bytes of
+   * LO(tab_body) hold them (a host env's debug image, section "tab_body": tests/test_tree_const.py reads it there and compares).  EnvWaveT::tree_accumulate walks it
+   * with every index a constant; vnl_env_create selects this kernel only for an env whose fused parents equal it
+   * (vnl_same_tree). */
+  static constexpr unsigned char body_parent[53] = {
+      0,  0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 7,  12, 13, 14, 7,  16, 17, 18, 19, 20, 21, 22, 23, 24, 25,
+      26, 27, 28, 29, 30, 31, 32, 1,  34, 35, 36, 37, 38, 39, 40, 41, 1,  43, 44, 45, 46, 1,  48, 49, 50, 51};
+  static_assert((int)sizeof(body_parent) == D.nbody, "one parent per dynamic body");
 };
+/* Is `parent` (the fused model's body_parentid, nbody entries) the tree SP's kernels are compiled for? */
+template <class SP>
+inline bool vnl_same_tree(const int* parent, int nbody) {
+  if (nbody != SP::D.nbody) return false;
+  for (int b = 0; b < nbody; b++)
+    if (parent[b] != (int)SP::body_parent[b]) return false;
+  return true;
+}
 /* Domain randomisation (vnl_env_set_domain, vnl_env_set_body_domain): the same kernel as BASE, with the randomisable model
  * tables read per env from KernelConsts::dom instead of the shared DevModel tables -- five of the contact / actuator / dof
  * parameters (EnvWaveT::par), four of the bodies' inertial parameters (EnvWaveT::par_row, total_mass_inv).  Instantiated in
