@@ -479,6 +479,37 @@ int vnl_rollout_post(const vnl_post_desc*, int32_t num_envs, void* stream);
  * or log row (dst == src of one op is fine).  For envs with a domain the randomised kernels take the same entry. */
 int vnl_env_step_post(vnl_env*, const float* action, const vnl_state* state, const vnl_post_desc* desc, void* stream);
 
+/* ---- evaluation: scored episodes, one record per episode ----
+ * Each env scores its first K = episodes_per_env episodes and is ignored afterwards (K = 1: brax's EvalWrapper).  Per env e,
+ * after the wrapper decision above has produced the final done, steps and truncation:
+ *   c = count[e];  if c >= K: nothing of env e is written
+ *   run[e][k] += metrics[e][k] (k = 0..6);  run[e][7] += reward[e]            float32 adds, in step order
+ *   if done[e] != 0:
+ *     records[e][c] = { cur_frame - sub_clip_frame, clip_id, steps[e], truncation[e] (0 if null), run[e][0..8) }
+ *     run[e][:] = 0;  count[e] = c + 1
+ * A record is VNL_EVAL_WIDTH float32 words.  Start frame and clip are what the start-priority counting of
+ * vnl_env_reset_done_weighted reads, as they stand after the post-processing (i.e. before a fresh reset); with null frame
+ * pointers (all three or none) columns 0 and 1 hold -1.  The caller zeroes run and count; record rows at or beyond count[e]
+ * are never written.  run, count and records must not be rows of a post op.
+ * VNL_ERR_ARG (nothing launched, the field named) for a null desc, done, steps, reward, metrics, run, count or records, for
+ * episodes_per_env < 1 and for frame pointers partly null. */
+#define VNL_EVAL_WIDTH 12
+typedef struct vnl_eval_desc {
+  const float *done, *steps, *truncation /* or NULL */, *reward, *metrics /* [num_envs][7] */;
+  const int32_t *cur_frame, *sub_clip_frame, *clip_id; /* all three or none */
+  float* run;      /* [num_envs][8] */
+  int32_t* count;  /* [num_envs] */
+  float* records;  /* [num_envs][episodes_per_env][VNL_EVAL_WIDTH] */
+  int32_t episodes_per_env, pad_;
+} vnl_eval_desc;
+/* a launch of its own: for envs whose step is more than the kernel launch, after vnl_rollout_post */
+int vnl_rollout_eval(const vnl_eval_desc*, int32_t num_envs, void* stream);
+/* vnl_env_step, vnl_rollout_post(desc) and vnl_rollout_eval(eval) in ONE launch: the wave that has stepped env e runs the
+ * post-processing and then the scoring of env e; the same words in every buffer as the three launches in that order.  Both
+ * descriptors are validated as by their own entries and copied into the launch's arguments. */
+int vnl_env_step_post_eval(vnl_env*, const float* action, const vnl_state* state, const vnl_post_desc* desc,
+                           const vnl_eval_desc* eval, void* stream);
+
 /* ---- PPO loss head: everything of compute_ppo_intention_loss after the network forward passes ----
  * (reference ppo_imitation/intention_losses.py:26-87 compute_gae, :131-202 loss) in three small launches: GAE,
  * advantage normalisation, tanh-Normal log-prob and entropy, clipped surrogate, value loss, latent KL,

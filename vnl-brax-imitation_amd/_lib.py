@@ -121,6 +121,16 @@ class PostDesc(C.Structure):  # include/vnl.h: vnl_post_desc
                 ("pad_", C.c_int32), ("ops", PostOp * POST_MAX_OPS)]
 
 
+EVAL_WIDTH = 12  # include/vnl.h: VNL_EVAL_WIDTH
+EVAL_COLUMNS = ("start_frame", "clip_id", "steps", "truncation")  # then the seven metrics and the reward
+
+
+class EvalDesc(C.Structure):  # include/vnl.h: vnl_eval_desc
+    _fields_ = [(n, C.c_void_p) for n in ("done", "steps", "truncation", "reward", "metrics", "cur_frame", "sub_clip_frame",
+                                          "clip_id", "run", "count", "records")] + \
+               [("episodes_per_env", C.c_int32), ("pad_", C.c_int32)]
+
+
 class GatherOp(C.Structure):  # include/vnl.h: vnl_gather_op
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("T", C.c_int32), ("width", C.c_int32)]
 
@@ -181,8 +191,8 @@ class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device
 
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
-    "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_reset_done_weighted", "vnl_start_priority_update", "vnl_env_step", "vnl_env_step_post", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
-    "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
+    "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_reset_done_weighted", "vnl_start_priority_update", "vnl_env_step", "vnl_env_step_post", "vnl_env_step_post_eval", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
+    "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_rollout_eval", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
@@ -216,6 +226,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.vnl_env_step.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     if hasattr(lib, "vnl_env_step_post"):
         lib.vnl_env_step_post.argtypes = [vp, vp, C.POINTER(StatePtrs), C.POINTER(PostDesc), vp]
+    if hasattr(lib, "vnl_env_step_post_eval"):
+        lib.vnl_env_step_post_eval.argtypes = [vp, vp, C.POINTER(StatePtrs), C.POINTER(PostDesc), C.POINTER(EvalDesc), vp]
+        lib.vnl_rollout_eval.argtypes = [C.POINTER(EvalDesc), C.c_int32, vp]
     lib.vnl_env_fk.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     lib.vnl_env_debug.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.vnl_env_scratch.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int32)]

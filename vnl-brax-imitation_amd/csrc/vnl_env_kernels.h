@@ -96,6 +96,38 @@ VNL_HD void vnl_post_epilogue(const vnl_post_desc& d, const unsigned e, const un
   }
 }
 
+// The scoring of ONE env (include/vnl.h above vnl_eval_desc: the semantics of vnl_rollout_eval, whose kernel is this function
+// per env) by the wave that has just stepped and post-processed it (vnl_env_step_post_eval).  Lane i owns word i of the
+// record row: lanes 0..3 the header, lanes 4..11 the eight running sums.  Every load is requested before the first value is
+// used (the uniform ones -- count, done, steps, truncation, the three frame words -- by every lane: one broadcast request
+// each; an absent row reads a present one in its place and is not used), the stores are one vector store each for the run
+// words, the record row and the count: no atomics, no loop over words.  A store follows a load of the same address only in
+// the lane that loaded it and depends on the loaded value.
+VNL_HD void vnl_eval_epilogue(const vnl_eval_desc& d, const unsigned e, const unsigned lane) {
+  VNL_SYNC_GLOBAL();  // (done, steps, truncation and the frame rows: stored by other lanes of this wave)
+  const int K = d.episodes_per_env;
+  const int c = d.count[e];
+  const float done = d.done[e], steps = d.steps[e], trunc = (d.truncation ? d.truncation : d.done)[e];
+  const bool frames = d.cur_frame != nullptr;
+  const int cur = (frames ? d.cur_frame : d.count)[e], sub = (frames ? d.sub_clip_frame : d.count)[e];
+  const int clip = (frames ? d.clip_id : d.count)[e];
+  VNL_FOR(i, VNL_EVAL_WIDTH) {
+    const int k = i < 4 ? 0 : i - 4;  // (a header lane reads word 0 and does not use it)
+    float* run = d.run + (size_t)e * 8 + k;
+    const float x = *(k < 7 ? d.metrics + (size_t)e * 7 + k : d.reward + e), r0 = *run;
+    if (c < K) {
+      const float r = r0 + x;
+      const float head = i == 0 ? (frames ? (float)(cur - sub) : -1.f)
+                                : (i == 1 ? (frames ? (float)clip : -1.f) : (i == 2 ? steps : (d.truncation ? trunc : 0.f)));
+      if (i >= 4) *run = done != 0.f ? 0.f : r;
+      if (done != 0.f) d.records[((size_t)e * K + c) * VNL_EVAL_WIDTH + i] = i < 4 ? head : r;
+    }
+  }
+  VNL_SERIAL {
+    if (c < K && done != 0.f) d.count[e] = c + 1;
+  }
+}
+
 // One env per 64-lane workgroup; the env's whole working set lives in dynamic LDS (~25 KB ->
 // 6 workgroups per CU, 1536 envs in flight on 256 CUs).  `post`: the rollout post-processing of this env as the wave's
 // epilogue (vnl_env_step_post), or num_ops < 0: none (vnl_env_step).
@@ -108,6 +140,23 @@ __global__ void VNL_ENV_KERNEL vnl_step_kernel(const KernelConsts* kc, DevState 
   w.step(action, dump_mid, trace);
   if (dump) w.dump(dump);
   if (post.num_ops >= 0) vnl_post_epilogue(post, blockIdx.x, threadIdx.x);
+}
+
+// The step kernel of an EVALUATION (vnl_env_step_post_eval): the step, the post-processing and then the scoring of this env
+// (vnl_eval_epilogue).  A kernel of its own, instantiated in a translation unit of its own (csrc/vnl_eval.hip), and not a
+// second descriptor of vnl_step_kernel: with the descriptor as an argument the specialised training kernel took one more
+// VGPR (242 for 241) although it never scores -- this way the kernels a rollout launches are compiled from the text they
+// had before evaluations were scored on the device.
+template <class SP>
+__global__ void VNL_ENV_KERNEL vnl_step_eval_kernel(const KernelConsts* kc, DevState st, const vreal* action, vreal* dump,
+                                                    vreal* dump_mid, int* trace, vnl_post_desc post, vnl_eval_desc ev) {
+  VNL_LDS_DECL(lds);
+  const VNL_CAS KernelConsts* k = VNL_TO_CAS(KernelConsts, kc);
+  EnvWaveT<SP> w{k->m, k->ev, st, k->L, lds, blockIdx.x, threadIdx.x, k, nullptr};
+  w.step(action, dump_mid, trace);
+  if (dump) w.dump(dump);
+  vnl_post_epilogue(post, blockIdx.x, threadIdx.x);
+  vnl_eval_epilogue(ev, blockIdx.x, threadIdx.x);
 }
 
 template <class SP>

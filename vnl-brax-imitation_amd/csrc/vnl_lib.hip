@@ -1074,6 +1074,10 @@ int vnl_domain_reset_(const KernelConsts* kc, int spec, int B, size_t lds, void*
                       const vreal* noise, vreal* dump, int* trace);
 int vnl_domain_step_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds, const vreal* action,
                      vreal* dump, vreal* dump_mid, int* trace, const vnl_post_desc& post);
+// .. and of the scoring step kernels, shared model and randomised (csrc/vnl_eval.hip: a translation unit of their own)
+int vnl_eval_step_(const KernelConsts* kc, int spec, int dom, int B, size_t lds, void* stream, const DevState& ds,
+                   const vreal* action, vreal* dump, vreal* dump_mid, int* trace, const vnl_post_desc& post,
+                   const vnl_eval_desc& ev);
 int vnl_domain_reset_done_(const KernelConsts* kc, int spec, int B, size_t lds, void* stream, const DevState& ds,
                            const ResetDoneArgs& a, vreal* dump, int* trace);
 int vnl_domain_redraw_(const KernelConsts* kc, int spec, int B, void* stream, const float* mask, const int64_t* step_base,
@@ -1206,8 +1210,27 @@ static int post_desc_check(const vnl_post_desc* desc, int32_t num_envs) {
   return VNL_OK;
 }
 
-// `post`: the descriptor the step waves run as their epilogue, or null (num_ops < 0 in the kernel: no epilogue)
-static int env_step_launch(vnl_env* env, const float* action, const vnl_state* state, const vnl_post_desc* post, void* stream) {
+// (vnl_rollout_eval and vnl_env_step_post_eval: one validation, one set of messages, each naming its field)
+static int eval_desc_check(const vnl_eval_desc* d, int32_t num_envs) {
+  if (!d) return fail(VNL_ERR_ARG, "vnl_rollout_eval: desc is null");
+  if (num_envs <= 0) return fail(VNL_ERR_ARG, "vnl_rollout_eval: num_envs must be positive");
+  if (!d->done) return fail(VNL_ERR_ARG, "vnl_eval_desc: done is null");
+  if (!d->steps) return fail(VNL_ERR_ARG, "vnl_eval_desc: steps is null");
+  if (!d->reward) return fail(VNL_ERR_ARG, "vnl_eval_desc: reward is null");
+  if (!d->metrics) return fail(VNL_ERR_ARG, "vnl_eval_desc: metrics is null");
+  if (!d->run) return fail(VNL_ERR_ARG, "vnl_eval_desc: run is null");
+  if (!d->count) return fail(VNL_ERR_ARG, "vnl_eval_desc: count is null");
+  if (!d->records) return fail(VNL_ERR_ARG, "vnl_eval_desc: records is null");
+  if (d->episodes_per_env < 1) return fail(VNL_ERR_ARG, "vnl_eval_desc: episodes_per_env must be at least 1");
+  if (!d->cur_frame != !d->sub_clip_frame || !d->cur_frame != !d->clip_id)
+    return fail(VNL_ERR_ARG, "vnl_eval_desc: cur_frame, sub_clip_frame and clip_id go together (all three or none)");
+  return VNL_OK;
+}
+
+// `post`: the descriptor the step waves run as their epilogue, or null (num_ops < 0 in the kernel: no epilogue); `ev` (with
+// `post`): the scoring after it -- the launch of vnl_step_eval_kernel -- or null
+static int env_step_launch(vnl_env* env, const float* action, const vnl_state* state, const vnl_post_desc* post,
+                           const vnl_eval_desc* ev, void* stream) {
   DevState ds;
   int rc = to_dev_state(state, &ds);
   if (rc != VNL_OK) return rc;
@@ -1216,6 +1239,12 @@ static int env_step_launch(vnl_env* env, const float* action, const vnl_state* s
   vnl_post_desc none{};
   none.num_ops = -1;
   const vnl_post_desc& pd = post ? *post : none;
+  if (ev) {
+    HIPCHK((hipError_t)vnl_eval_step_(env->kc, env->spec, env->has_dom, env->B, env->lds_bytes, stream, ds, (const vreal*)action,
+                                      env->debug == 1 ? env->dump : nullptr, env->debug == 2 ? env->dump : nullptr,
+                                      env->debug ? env->trace : nullptr, pd, *ev));
+    return VNL_OK;
+  }
   if (env->has_dom) {
     HIPCHK((hipError_t)vnl_domain_step_(env->kc, env->spec, env->B, env->lds_bytes, stream, ds, (const vreal*)action,
                                         env->debug == 1 ? env->dump : nullptr, env->debug == 2 ? env->dump : nullptr,
@@ -1236,7 +1265,7 @@ static int env_step_launch(vnl_env* env, const float* action, const vnl_state* s
 
 extern "C" int vnl_env_step(vnl_env* env, const float* action, const vnl_state* state, void* stream) {
   if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step: null argument");
-  return env_step_launch(env, action, state, nullptr, stream);
+  return env_step_launch(env, action, state, nullptr, nullptr, stream);
 }
 
 // The step with vnl_rollout_post(desc, num_envs = the env's B) as the epilogue of each step wave (include/vnl.h)
@@ -1245,7 +1274,18 @@ extern "C" int vnl_env_step_post(vnl_env* env, const float* action, const vnl_st
   if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step_post: null argument");
   int rc = post_desc_check(desc, env->B);
   if (rc != VNL_OK) return rc;
-  return env_step_launch(env, action, state, desc, stream);
+  return env_step_launch(env, action, state, desc, nullptr, stream);
+}
+
+// .. and with vnl_rollout_eval(eval, num_envs = the env's B) after it in the same wave (include/vnl.h)
+extern "C" int vnl_env_step_post_eval(vnl_env* env, const float* action, const vnl_state* state, const vnl_post_desc* desc,
+                                      const vnl_eval_desc* eval, void* stream) {
+  if (!env || !action || !state) return fail(VNL_ERR_ARG, "vnl_env_step_post_eval: null argument");
+  int rc = post_desc_check(desc, env->B);
+  if (rc != VNL_OK) return rc;
+  rc = eval_desc_check(eval, env->B);
+  if (rc != VNL_OK) return rc;
+  return env_step_launch(env, action, state, desc, eval, stream);
 }
 
 // Domain randomisation (brax / MJX semantics: raw fields are replaced, the derived constants -- dof / body invweight0,
@@ -1809,6 +1849,18 @@ extern "C" int vnl_rollout_post(const vnl_post_desc* desc, int32_t num_envs, voi
   return VNL_OK;
 }
 
+// ---- evaluation records (include/vnl.h: vnl_rollout_eval) ---------------------------------------
+// One wave per env runs vnl_eval_epilogue (csrc/vnl_env_kernels.h), the code the step waves run in vnl_env_step_post_eval.
+__global__ void __launch_bounds__(64) vnl_eval_kernel(vnl_eval_desc d) { vnl_eval_epilogue(d, blockIdx.x, threadIdx.x); }
+
+extern "C" int vnl_rollout_eval(const vnl_eval_desc* desc, int32_t num_envs, void* stream) {
+  int rc = eval_desc_check(desc, num_envs);
+  if (rc != VNL_OK) return rc;
+  hipLaunchKernelGGL(vnl_eval_kernel, dim3(num_envs), dim3(64), 0, (hipStream_t)stream, *desc);
+  HIPCHK(hipGetLastError());
+  return VNL_OK;
+}
+
 // ---- PPO loss head (include/vnl.h: vnl_ppo_head) -------------------------------------------------
 // Three launches on the caller's stream: (1) GAE, one column per thread, + advantage / reward statistics;
 // (2) the per-sample head, 32 lanes per sample (lane = action component: coalesced rows, shuffle sums),
@@ -2153,4 +2205,5 @@ extern "C" int vnl_start_priority_update(uint32_t* ended, uint32_t* failed, uint
 #ifdef VNL_FORKJOIN_DEFINED
 // host simulation (tests/hostsim): this file is its one translation unit, so the randomised instantiations come in here
 #include "vnl_domain.hip"
+#include "vnl_eval.hip"
 #endif

@@ -735,8 +735,13 @@ class RodentTracking(Env):
             ev[0].record()
         # one-shot hand-over from the fused unroll (acting._generate_unroll_fused): the rollout post-processing of this step
         # runs as the step kernel's epilogue (vnl_env_step_post) -- inside the launch the events time
+        # (.. and, from acting.evaluate_unroll, the scoring of the step after it: vnl_env_step_post_eval)
         post, self._post_desc = getattr(self, "_post_desc", None), None
-        if post is not None:
+        score, self._eval_desc = getattr(self, "_eval_desc", None), None
+        if post is not None and score is not None:
+            _lib.check(self._L, self._L.vnl_env_step_post_eval(self._env_h, a.data_ptr(), C.byref(p), C.byref(post),
+                                                               C.byref(score), self._stream()))
+        elif post is not None:
             _lib.check(self._L, self._L.vnl_env_step_post(self._env_h, a.data_ptr(), C.byref(p), C.byref(post), self._stream()))
         else:
             _lib.check(self._L, self._L.vnl_env_step(self._env_h, a.data_ptr(), C.byref(p), self._stream()))

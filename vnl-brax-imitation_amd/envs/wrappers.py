@@ -110,6 +110,7 @@ class AutoResetWrapper(Wrapper):
             raise ValueError("start_priority needs mode='fresh': the cached first state has one start frame")
         self.reset_info, self.start_priority = reset_info_on_autoreset, start_priority
         self.mode, self.seed, self.env_offset = mode, int(seed), int(env_offset)
+        self.before_reset = None  # EvalWrapper's scoring, for the length of its step: sees a finished episode before the fresh reset
 
     def reset(self, rng=None, *, reset_step=None, **kw) -> State:
         """`reset_step` (mode="fresh"): the value the counter starts from, an int or int64 [1] tensor -- a resumed run's;
@@ -148,6 +149,8 @@ class AutoResetWrapper(Wrapper):
         state = self.env.step(state, action)
         if self.mode == "fresh":
             counter = state.info["reset_step"]
+            if self.before_reset is not None:
+                self.before_reset(state)
             self.env.unwrapped.reset_done(state, state.done, seed=self.seed, step_base=counter, env_offset=self.env_offset,
                                           **self.priority_args(state))
             counter.add_(1)
@@ -172,7 +175,22 @@ class EvalMetrics:
 
 
 class EvalWrapper(Wrapper):
-    """Accumulates per-episode metrics of the first episode of every env (brax EvalWrapper)."""
+    """Accumulates per-episode metrics of the first episode of every env (brax EvalWrapper): info["eval_metrics"].
+
+    Beside it, the scored episodes of include/vnl.h vnl_eval_desc in torch ops (the restatement the device's records are
+    compared with, bit for bit): each env scores its first `episodes_per_env` episodes.  info["eval_run"] (B, 8) float32 are
+    the running sums of the seven metrics and the reward, info["eval_count"] (B,) int32 the episodes completed,
+    info["eval_records"] (B, K, 12) float32 one row per completed episode: start frame, clip, steps, truncation, the eight
+    sums (`_lib.EVAL_COLUMNS`).  A tracking env of this library sums the seven columns of its metrics buffer, as the kernel
+    does, whichever of them its `State.metrics` names (`columns`: name -> column of the sums).  Rows at or beyond the count
+    stay zero.  Under AutoResetWrapper(mode="fresh") the step is
+    scored before the fresh reset rewrites the frame counters."""
+
+    def __init__(self, env: Env, episodes_per_env: int = 1):
+        super().__init__(env)
+        if int(episodes_per_env) < 1:
+            raise ValueError("episodes_per_env must be at least 1")
+        self.episodes_per_env = int(episodes_per_env)
 
     def reset(self, rng=None, **kw) -> State:
         state = self.env.reset(rng, **kw)
@@ -182,11 +200,73 @@ class EvalWrapper(Wrapper):
             active_episodes=torch.ones_like(state.reward),
             episode_steps=torch.zeros_like(state.reward),
         )
+        B, dev = state.reward.shape[0], state.reward.device
+        buf = self._metrics_buffer(state)
+        if buf is not None:  # (State.metrics are column views of it)
+            self.columns = {k: v.storage_offset() - buf.storage_offset() for k, v in state.metrics.items()}
+        else:
+            self.columns = {k: i for i, k in enumerate(state.metrics)}
+        n = 1 + (buf.shape[1] if buf is not None else len(state.metrics))
+        self.columns["reward"] = n - 1
+        state.info["eval_run"] = torch.zeros((B, n), dtype=torch.float32, device=dev)
+        state.info["eval_count"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        state.info["eval_records"] = torch.zeros((B, self.episodes_per_env, 4 + n), dtype=torch.float32, device=dev)
         return state
+
+    @staticmethod
+    def _metrics_buffer(state: State):
+        raw = state.info.get("_raw")
+        return raw["metrics"] if isinstance(raw, dict) and "metrics" in raw else None
+
+    def _fresh(self):
+        ar = self.env
+        return ar if isinstance(ar, AutoResetWrapper) and ar.mode == "fresh" else None
+
+    def score(self, state: State) -> None:
+        """vnl_rollout_eval in torch ops, on the state as the wrappers below have left it."""
+        info, K = state.info, self.episodes_per_env
+        run, count, rec = info["eval_run"], info["eval_count"], info["eval_records"]
+        live = count < K
+        buf = self._metrics_buffer(state)
+        x = torch.cat([buf if buf is not None else torch.stack(list(state.metrics.values()), dim=1), state.reward[:, None]],
+                      dim=1).to(torch.float32)
+        r = run + x
+        done = (state.done != 0) & live
+        if all(k in info for k in ("cur_frame", "sub_clip_frame", "clip_id")):
+            start, clip = (info["cur_frame"] - info["sub_clip_frame"]).to(torch.float32), info["clip_id"].to(torch.float32)
+        else:
+            start = clip = torch.full_like(state.reward, -1.0, dtype=torch.float32)
+        trunc = info["truncation"] if "truncation" in info else torch.zeros_like(state.reward)
+        row = torch.cat([torch.stack([start, clip, info["steps"].to(torch.float32), trunc.to(torch.float32)], dim=1), r], dim=1)
+        env = torch.arange(rec.shape[0], device=rec.device)
+        slot = count.clamp(max=K - 1).long()
+        rec[env, slot] = torch.where(done[:, None], row, rec[env, slot])
+        run.copy_(torch.where(live[:, None], torch.where(done[:, None], torch.zeros_like(r), r), run))
+        count += done.to(torch.int32)
+
+    def sync_eval_metrics(self, state: State) -> None:
+        """info["eval_metrics"] from the records (the fused routes keep only those): the first episode of every env, or what
+        has run of it."""
+        em: EvalMetrics = state.info["eval_metrics"]
+        run, rec = state.info["eval_run"], state.info["eval_records"]
+        fin = state.info["eval_count"] >= 1
+        for name, k in self.columns.items():
+            em.episode_metrics[name].copy_(torch.where(fin, rec[:, 0, 4 + k], run[:, k]))
+        em.episode_steps.copy_(torch.where(fin, rec[:, 0, 2], state.info["steps"]))
+        em.active_episodes.copy_((~fin).to(em.active_episodes.dtype))
 
     def step(self, state: State, action: torch.Tensor) -> State:
         em: EvalMetrics = state.info["eval_metrics"]
-        nstate = self.env.step(state, action)
+        ar = self._fresh()
+        if ar is not None:
+            ar.before_reset = self.score
+        try:
+            nstate = self.env.step(state, action)
+        finally:
+            if ar is not None:
+                ar.before_reset = None
+        if ar is None:
+            self.score(nstate)
         active = em.active_episodes
         em.episode_steps.copy_(torch.where(active.bool(), nstate.info["steps"], em.episode_steps))
         for k, acc in em.episode_metrics.items():

@@ -45,11 +45,15 @@ def actor_step(env, env_state: State, policy, key, extra_fields: Sequence[str] =
                               extras={"policy_extras": policy_extras, "state_extras": state_extras})
 
 
-def _fusable(env):
+def _fusable(env, through_eval: bool = False):
     """AutoReset(Episode(RodentTracking)) with action_repeat 1 on the native library: the wrappers and the
-    Transition logging of one step then collapse into ONE launch of vnl_rollout_post."""
+    Transition logging of one step then collapse into ONE launch of vnl_rollout_post.  `through_eval`: the same under an
+    EvalWrapper, for `evaluate_unroll`, which scores the steps on the device (a rollout that logged Transitions through
+    the fused route would leave the wrapper's scores behind)."""
     from ..envs import wrappers as W
 
+    if through_eval and isinstance(env, W.EvalWrapper):
+        env = env.env
     if not isinstance(env, W.AutoResetWrapper) or not isinstance(env.env, W.EpisodeWrapper):
         return None
     ep, base = env.env, env.env.env
@@ -259,6 +263,168 @@ class GraphedUnroll:
         return self.state, self.data
 
 
+# Private switch (tests compare the two): the scoring of an evaluation step runs in the step kernel's launch
+# (vnl_env_step_post_eval); False = three launches, vnl_env_step + vnl_rollout_post + vnl_rollout_eval, which an env whose
+# `step` does more than launch the kernel (AntTracking) takes in any case.
+_EVAL_EPILOGUE = True
+
+
+def _eval_fusable(env):
+    """EvalWrapper(AutoReset(Episode(tracking env))), action_repeat 1, on a library with the scoring entries"""
+    from ..envs import wrappers as W
+
+    fz = _fusable(env, through_eval=True) if isinstance(env, W.EvalWrapper) else None
+    if fz is None or not hasattr(fz[2]._L, "vnl_rollout_eval"):
+        return None
+    return fz
+
+
+def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int) -> State:
+    """`unroll_length` evaluation steps with no Transition log: per step the policy, ONE launch that steps, applies the
+    Episode / AutoReset wrappers (its ops are the first-state restores only, every log pointer null) and scores
+    (vnl_env_step_post_eval) and, with AutoResetWrapper(mode="fresh"), vnl_env_reset_done with no logs.  The device-noise
+    and reset counters advance once, after the loop, as in `_generate_unroll_fused`."""
+    import ctypes as C
+
+    from .. import _lib
+    from ..envs.rodent import RodentTracking
+
+    ar, ep, base = fz
+    T, info, dev = unroll_length, st.info, st.obs.device
+    B = st.obs.shape[0]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+    raw = info["_raw"]
+    prev_done = st.done.clone()
+    d = _lib.PostDesc()
+    d.steps, d.prev_done, d.done, d.truncation, d.reward = (ptr(info["steps"]), ptr(prev_done), ptr(st.done),
+                                                            ptr(info["truncation"]), ptr(st.reward))
+    d.episode_length, d.action_repeat = ep.episode_length, 1
+    fresh = getattr(ar, "mode", "first_state") == "fresh"
+    ops = []
+    if not fresh:
+        fps = info["first_pipeline_state"]
+        for name in st.pipeline_state._FIELDS:
+            cur = st.pipeline_state.raw(name)
+            ops.append((cur, fps.raw(name)))
+        ops.append((st.obs, info["first_obs"]))
+        if ar.reset_info:
+            ops += [(info[k2], v) for k2, v in info["first_info"].items()]
+    d.num_ops = len(ops)
+    for o, (cur, first) in zip(d.ops, ops):
+        assert cur.dtype in (torch.float32, torch.int32) and cur.is_contiguous() and first.is_contiguous()
+        o.dst, o.src, o.first, o.log, o.width = ptr(cur), ptr(cur), ptr(first), C.c_void_p(0), 1 if cur.dim() == 1 else cur.shape[1]
+    e = _lib.EvalDesc()
+    e.done, e.steps, e.truncation, e.reward, e.metrics = (ptr(st.done), ptr(info["steps"]), ptr(info["truncation"]),
+                                                          ptr(st.reward), ptr(raw["metrics"]))
+    e.cur_frame, e.sub_clip_frame, e.clip_id = ptr(raw["cur_frame"]), ptr(raw["sub_clip_frame"]), ptr(raw["clip_id"])
+    e.run, e.count, e.records = ptr(info["eval_run"]), ptr(info["eval_count"]), ptr(info["eval_records"])
+    e.episodes_per_env = ew.episodes_per_env
+    assert info["eval_records"].shape[1:] == (ew.episodes_per_env, _lib.EVAL_WIDTH) and info["eval_run"].shape[1] == 8
+    epilogue = _EVAL_EPILOGUE and hasattr(base._L, "vnl_env_step_post_eval") and type(base).step is RodentTracking.step
+    dev_noise = _device_noise(policy)
+    for t in range(T):
+        if dev_noise:
+            actions, _ = policy(info["traj"], st.obs, None, step_offset=t, advance=False)
+        else:
+            actions, _ = policy(info["traj"], st.obs, key)
+        if epilogue:  # (the descriptors are copied into the launch's arguments by the call)
+            base._post_desc, base._eval_desc = d, e
+            try:
+                base.step(st, actions)
+            finally:
+                base._post_desc = base._eval_desc = None
+        else:
+            base.step(st, actions)
+            _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
+            _lib.check(base._L, base._L.vnl_rollout_eval(C.byref(e), B, stream))
+        if fresh:
+            base.reset_done(st, st.done, seed=ar.seed, step_base=info["reset_step"], step_offset=t, env_offset=ar.env_offset)
+    _evaluate_unroll_fused.hold = prev_done  # the launches are asynchronous
+    if fresh:
+        info["reset_step"].add_(T)
+    if dev_noise:
+        policy.counter.add_(T)
+    return st
+
+
+def evaluate_unroll(env, env_state: State, policy, key, unroll_length: int, fused: Optional[bool] = None) -> State:
+    """`unroll_length` steps of EvalWrapper(...) `env` for their scores alone (info["eval_records"] and its companions): no
+    Transition is kept.  `fused` (default: whenever possible) runs the wrappers and the scoring on the device,
+    `_evaluate_unroll_fused`; otherwise the wrappers step in torch ops.  The two give the same records, bit for bit."""
+    fz = _eval_fusable(env) if fused is not False else None
+    if fused is True and fz is None:
+        raise ValueError("fused evaluation needs EvalWrapper(AutoResetWrapper(EpisodeWrapper(<tracking env>))), action_repeat 1")
+    if fz is not None:
+        st = _evaluate_unroll_fused(env, fz, env_state, policy, key, unroll_length)
+        env.sync_eval_metrics(st)
+        return st
+    for _ in range(unroll_length):
+        actions, _ = policy(env_state.info["traj"], env_state.obs, key)
+        env_state = env.step(env_state, actions)
+    return env_state
+
+
+class GraphedEval:
+    """`evaluate_unroll` on the fused route with `graph_steps` steps captured ONCE into a hipGraph: an evaluation of
+    `unroll_length` steps is `unroll_length // graph_steps` replays and an eager tail of the remaining steps.  Same kernels,
+    same arguments, same streams of noise as the eager fused route: the same records.
+
+    The graph works on the buffers of the `env_state` given here; `__call__(state)` copies another state of the same env
+    (a new `env.reset`) into them first.  The policy's parameter tensors are fixed likewise (update them in place).  A
+    generator policy needs `key` on the device (registered with the graph); a device-noise policy carries step offsets
+    0..graph_steps-1 in the captured launches and the graph's last node advances its counter, as in GraphedUnroll."""
+
+    def __init__(self, env, env_state: State, policy, key, unroll_length: int, graph_steps: int = 20):
+        fz = _eval_fusable(env)
+        dev = env_state.obs.device
+        if fz is None or dev.type != "cuda":
+            raise ValueError("GraphedEval needs EvalWrapper(AutoResetWrapper(EpisodeWrapper(<env on a HIP device>))), action_repeat 1")
+        dev_noise = _device_noise(policy)
+        if not dev_noise and (key is None or key.device.type != "cuda"):
+            raise ValueError("GraphedEval needs a torch.Generator on the device (its stream is captured with the graph)")
+        self.env, self.state, self.policy, self.key = env, env_state, policy, key
+        self.graph_steps = max(1, min(int(graph_steps), int(unroll_length)))
+        self.replays, self.tail = divmod(int(unroll_length), self.graph_steps)
+        self._fz = fz
+        args = (env, fz, env_state, policy, key, self.graph_steps)
+        # warm-up on a side stream with everything put back afterwards, as in GraphedUnroll
+        gen_state = policy.counter.clone() if dev_noise else key.get_state()
+        saved = _snapshot_state(env_state)
+        base = fz[0].unwrapped
+        saved_domain = (base._copy_domain_tables() if getattr(base, "domain_ranges", None) is not None or
+                        getattr(base, "body_domain_ranges", None) is not None else None)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            _evaluate_unroll_fused(*args)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        _restore_state(env_state, saved)
+        if saved_domain is not None:
+            base._copy_domain_tables(saved_domain)
+        self.graph = torch.cuda.CUDAGraph()
+        if dev_noise:
+            policy.counter.copy_(gen_state)
+        else:
+            key.set_state(gen_state)
+            self.graph.register_generator_state(key)
+        with torch.cuda.graph(self.graph):
+            _evaluate_unroll_fused(*args)
+        _restore_state(env_state, saved)
+
+    def __call__(self, state: Optional[State] = None) -> State:
+        if state is not None and state is not self.state:
+            for dst, src in zip(_state_tensors(self.state), _state_tensors(state)):
+                dst.copy_(src)
+        for _ in range(self.replays):
+            self.graph.replay()
+        if self.tail:
+            _evaluate_unroll_fused(self.env, self._fz, self.state, self.policy, self.key, self.tail)
+        self.env.sync_eval_metrics(self.state)
+        return self.state
+
+
 def _state_tensors(st: State):
     out = [st.pipeline_state.raw(n) for n in st.pipeline_state._FIELDS] + [st.obs, st.reward, st.done]
     for k in sorted(st.info):
@@ -267,6 +433,8 @@ def _state_tensors(st: State):
             out.append(v)
         elif isinstance(v, dict):
             out += [v[k2] for k2 in sorted(v) if isinstance(v[k2], torch.Tensor)]
+        elif hasattr(v, "_FIELDS") and hasattr(v, "raw"):  # (the cached first pipeline state of a first_state auto-reset)
+            out += [v.raw(n) for n in v._FIELDS]
     seen, uniq = set(), []
     for t in out:  # (info["_raw"] aliases obs / reward / ...: each storage once)
         if t.data_ptr() not in seen:
@@ -316,32 +484,97 @@ def _leaves(tr: Transition):
     return out
 
 
+def _clone_param(p):
+    if dataclasses.is_dataclass(p):
+        return dataclasses.replace(p, **{f.name: getattr(p, f.name).clone() for f in dataclasses.fields(p)
+                                         if isinstance(getattr(p, f.name), torch.Tensor)})
+    return p.clone() if isinstance(p, torch.Tensor) else p
+
+
+def _copy_params(dst, src) -> None:
+    """the (normaliser state, flat parameters) pair of make_inference_fn, in place"""
+    for a, b in zip(dst, src):
+        if isinstance(a, torch.Tensor):
+            a.copy_(b)
+        elif dataclasses.is_dataclass(a):
+            for f in dataclasses.fields(a):
+                if isinstance(getattr(a, f.name), torch.Tensor):
+                    getattr(a, f.name).copy_(getattr(b, f.name))
+
+
 class Evaluator:
-    """acting.py:84-156."""
+    """acting.py:84-156, with `episodes_per_env` scored episodes per env (envs/wrappers.py EvalWrapper; 1 = the reference).
+
+    The unroll is `episodes_per_env * episode_length // action_repeat` steps.  A fusable env (`_eval_fusable`) is stepped,
+    wrapped and scored on the device (`evaluate_unroll`); `graphed` (default: on a HIP device, when the policy draws
+    device noise or `key` lives on the device) replays `graph_steps` captured steps at a time (GraphedEval).  Any other env
+    goes through the generic `generate_unroll` loop.  `fused=False` forces that loop.
+    `records` is the (N, 12) float32 array of the last evaluation's completed episodes (`_lib.EVAL_COLUMNS`, then the seven
+    metrics and the reward), envs in order, each env's episodes in order."""
 
     def __init__(self, eval_env, eval_policy_fn, num_eval_envs: int, episode_length: int, action_repeat: int,
-                 key: Optional[torch.Generator]):
+                 key: Optional[torch.Generator], episodes_per_env: int = 1, graphed: Optional[bool] = None,
+                 graph_steps: int = 20, fused: Optional[bool] = None):
         self._key = key
         self._eval_walltime = 0.0
-        self._env = EvalWrapper(eval_env)
+        self._K = int(episodes_per_env)
+        self._env = EvalWrapper(eval_env, episodes_per_env=self._K)
         self._policy_fn = eval_policy_fn
-        self._unroll = episode_length // action_repeat
-        self._steps_per_unroll = episode_length * num_eval_envs
+        self._unroll = self._K * episode_length // action_repeat
+        self._steps_per_unroll = self._K * episode_length * num_eval_envs
+        self._fused = fused is not False and _eval_fusable(self._env) is not None
+        if fused is True and not self._fused:
+            raise ValueError("fused evaluation needs AutoResetWrapper(EpisodeWrapper(<tracking env>)), action_repeat 1")
+        self._graphed, self._graph_steps, self._graph = graphed, int(graph_steps), None
+        self.records: Optional[np.ndarray] = None
+        self.state: Optional[State] = None  # the eval envs as the last evaluation left them
+
+    def _unroll_state(self, policy_params) -> State:
+        """the state after the evaluation's unroll, by the route chosen at construction"""
+        state = self._env.reset(self._key)
+        if not self._fused:
+            state, _ = generate_unroll(self._env, state, self._policy_fn(policy_params), self._key, self._unroll)
+            return state
+        if self._graph is None:
+            policy = self._policy_fn(policy_params)
+            on_dev = state.obs.device.type == "cuda"
+            can = on_dev and (_device_noise(policy) or (self._key is not None and self._key.device.type == "cuda"))
+            if self._graphed and not can:
+                raise ValueError("a graphed evaluation needs a HIP device and device noise or a generator on the device")
+            if not (can if self._graphed is None else self._graphed):
+                return evaluate_unroll(self._env, state, policy, self._key, self._unroll, fused=True)
+            # (the graph reads fixed parameter tensors: copies of its own, refreshed before every evaluation)
+            self._params = tuple(_clone_param(p) for p in policy_params)
+            self._graph = GraphedEval(self._env, state, self._policy_fn(self._params), self._key, self._unroll,
+                                      graph_steps=self._graph_steps)
+        _copy_params(self._params, policy_params)
+        return self._graph(state)
 
     def run_evaluation(self, policy_params, training_metrics: Dict[str, Any], aggregate_episodes: bool = True):
         t = time.time()
-        state = self._env.reset(self._key)
-        state, _ = generate_unroll(self._env, state, self._policy_fn(policy_params), self._key, self._unroll)
+        state = self.state = self._unroll_state(policy_params)
         em = state.info["eval_metrics"]
         if em.active_episodes.is_cuda:
             torch.cuda.synchronize(em.active_episodes.device)
         epoch_eval_time = time.time() - t
+        count = state.info["eval_count"].cpu().numpy()
+        recs = state.info["eval_records"].cpu().numpy()
+        self.records = recs[np.arange(recs.shape[1])[None, :] < count[:, None]]
         metrics = {}
+        if self._K == 1:
+            per_episode = {name: v.cpu().numpy() for name, v in em.episode_metrics.items()}
+            lengths = em.episode_steps.cpu().numpy()
+        else:  # over all completed episodes
+            per_episode = {name: self.records[:, 4 + self._env.columns[name]] for name in em.episode_metrics}
+            lengths = self.records[:, 2]
         for fn in (np.mean, np.std):
             suffix = "_std" if fn is np.std else ""
-            metrics.update({f"eval/episode_{name}{suffix}": (fn(v.cpu().numpy()) if aggregate_episodes else v.cpu().numpy())
-                            for name, v in em.episode_metrics.items()})
-        metrics["eval/avg_episode_length"] = float(np.mean(em.episode_steps.cpu().numpy()))
+            metrics.update({f"eval/episode_{name}{suffix}": (fn(v) if aggregate_episodes else v)
+                            for name, v in per_episode.items()})
+        metrics["eval/avg_episode_length"] = float(np.mean(lengths))
+        if self._K > 1:
+            metrics["eval/episodes_scored"] = int(self.records.shape[0])
+            metrics["eval/truncated_fraction"] = float(np.mean(self.records[:, 3] != 0))
         metrics["eval/epoch_eval_time"] = epoch_eval_time
         metrics["eval/sps"] = self._steps_per_unroll / epoch_eval_time
         self._eval_walltime += epoch_eval_time

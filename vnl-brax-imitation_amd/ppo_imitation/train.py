@@ -152,6 +152,8 @@ def train(
     body_domain_ranges=None,
     body_domain_shared=(),
     body_inertia_with_mass: bool = False,
+    eval_episodes_per_env: int = 1,
+    eval_auto_reset: str = "first_state",
 ):
     """PPO training (train.py:62-491).
 
@@ -184,7 +186,7 @@ def train(
     reference); "fresh" = it starts a new episode with its own start frame, clip and reset noise, drawn on the device inside
     the unroll (envs/wrappers.py AutoResetWrapper, vnl_env_reset_done) from streams keyed by (a seed derived from `seed`,
     step, rank * (num_envs // world) + env index): like the device policy noise, independent of the sharding.  The
-    evaluator's env keeps "first_state" (EvalWrapper scores each env's first episode only).  The counter of the draws is
+    evaluator's env keeps "first_state" unless `eval_auto_reset` says otherwise (below).  The counter of the draws is
     `TrainingState.reset_step` (checkpoint.save_params(reset_step=...) / `restore_from` carry it, like `policy_counter`).
 
     `start_priority`: False, True or dict(prior=, floor_q16=, decay_shift=); needs auto_reset="fresh".  The fresh resets
@@ -201,16 +203,26 @@ def train(
     first episodes get theirs at the wrapper's reset; bound after `randomization_fn`, whose values an env keeps until its
     first redraw.  The draws are keyed like those of the fresh reset (rank * (num_envs // world) + env index): nothing more
     is needed with several ranks.  The evaluator's env gets the ranges and ONE draw, on the eval seed: its later episodes are
-    not redrawn, as its auto-reset is not fresh (EvalWrapper scores first episodes only).  A checkpoint does not carry the
+    not redrawn, as its auto-reset is not fresh (with eval_auto_reset="fresh", below, they are).  A checkpoint does not carry the
     tables: a resumed run resets its envs once more, with the initial draw made at the resumed counter.
     `body_domain_ranges` (`body_domain_shared`, `body_inertia_with_mass`: envs/rodent.py with_body_domain_ranges /
     body_domain_ranges_scaled) does the same for body mass, principal moments and centre of mass, under the same rules.
+
+    `eval_episodes_per_env` (K) and `eval_auto_reset`: the evaluator scores the first K episodes of every eval env, one
+    record per episode (acting.Evaluator, envs/wrappers.py EvalWrapper; `train.last_evaluator.records`), over an unroll of
+    K * episode_length // action_repeat steps; K > 1 adds eval/episodes_scored and eval/truncated_fraction and takes the
+    eval/episode_* statistics over all completed records.  With eval_auto_reset="fresh" the eval env's later episodes are new
+    ones -- start frame, clip and reset noise drawn on the device on the eval seed -- and `domain_ranges` /
+    `body_domain_ranges` go to its wrapper, so that every eval episode has a domain of its own; start priorities stay off
+    for the evaluator.  The defaults are the reference's evaluation: K = 1 from the cached first state.
 
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
     ~500 launches of microsecond kernels and purely launch-bound.
     """
     dist, rank, world = _dist_info()
+    if eval_auto_reset not in env_wrappers.AUTO_RESET_MODES:
+        raise ValueError(f"unknown eval_auto_reset {eval_auto_reset!r}: expected one of {env_wrappers.AUTO_RESET_MODES}")
     assert batch_size * num_minibatches % num_envs == 0
     assert num_envs % world == 0 and batch_size % world == 0
     local_envs, local_batch = num_envs // world, batch_size // world
@@ -627,7 +639,13 @@ def train(
         ev_wrapped = env_wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat,
                                        randomization_fn=bind_randomization(randomization_fn, num_eval_envs, seed * 31 + 7),
                                        reset_info_on_autoreset=reset_info_on_autoreset)
-        if domain_ranges is not None or body_domain_ranges is not None:  # one draw on the eval seed; first_state auto-reset keeps it (see the docstring)
+        if eval_auto_reset == "fresh":  # new episodes, each with its own domain, on the eval seed
+            ev_wrapped = env_wrappers.wrap(ev_wrapped.unwrapped, episode_length=episode_length, action_repeat=action_repeat,
+                                           auto_reset="fresh", auto_reset_seed=seed * 31 + 7, domain_ranges=domain_ranges,
+                                           domain_shared=domain_shared, body_domain_ranges=body_domain_ranges,
+                                           body_domain_shared=body_domain_shared,
+                                           body_inertia_with_mass=body_inertia_with_mass)
+        elif domain_ranges is not None or body_domain_ranges is not None:  # one draw on the eval seed; first_state auto-reset keeps it (see the docstring)
             ev_base = ev_wrapped.unwrapped
             if domain_ranges is not None:
                 ev_base = ev_base.with_domain_ranges(domain_ranges, shared=domain_shared)
@@ -639,7 +657,7 @@ def train(
                                            reset_info_on_autoreset=reset_info_on_autoreset)
         evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval, **eval_kw),
                                      num_eval_envs=num_eval_envs, episode_length=episode_length,
-                                     action_repeat=action_repeat, key=g_eval)
+                                     action_repeat=action_repeat, key=g_eval, episodes_per_env=eval_episodes_per_env)
 
     def inference_params():
         return (training_state.normalizer_params.clone(), training_state.params.detach()[:n_pol].clone())
@@ -689,4 +707,5 @@ def train(
     train.last_env_state = env_state  # the training envs as the run leaves them
     train.last_env = env  # .. and the wrapped env they belong to (its `unwrapped` holds the per-env domain tables)
     train.last_start_priority = prio  # the StartPriority of the run (None without start_priority)
+    train.last_evaluator = evaluator  # its `records`: the scored episodes of the last evaluation
     return make_policy, params, metrics
