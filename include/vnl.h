@@ -443,6 +443,30 @@ int vnl_policy_forward_noise(vnl_policy*, const float* params, const float* obs_
                              int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
                              float* latent_mean, float* latent_logvar, float* rand_log_prob /* or NULL */, void* stream);
 
+/* Latent-driven acting: the DECODER alone, [z | normalised obs] -> [Dense -> ReLU -> LayerNorm] x (n-1) -> Dense -> the
+ * tanh-Normal tail of vnl_policy_forward, on the same handle, flat parameter buffer and vnl_policy_spec; only the decoder's
+ * parameters are read (the encoder's and the two latent heads' are not).  latent is [batch][latent].  Fed
+ * z = latent_mean + eps_latent * exp(latent_logvar / 2) of a vnl_policy_forward call, it returns that call's outputs up to
+ * the rounding of z.
+ * vnl_policy_decode: z, eps_action and rand_action are the caller's; a null latent is VNL_ERR_ARG.
+ * vnl_policy_decode_noise: the streams, counters and step of vnl_policy_noise above, keyed by (seed, step, env_offset + row):
+ *   stream 1  eps_action, stream 2 the random action shared by the batch -- the draws vnl_policy_forward_noise makes;
+ *   stream 0  with latent == NULL, z ITSELF is the normal draw, z ~ N(0, I): the prior of the KL term, on the counters the
+ *             acting kernel uses for eps_latent; recorded through eps_latent_out when that is given.  With latent given,
+ *             stream 0 is not drawn and eps_latent_out is left alone.
+ * deterministic: streams 1 and 2 are not drawn.  The kernel only READS the step counter.  VNL_ERR_ARG (nothing launched)
+ * for obs_mean / obs_std given one without the other, batch outside 1..max_batch, a null step_base, a negative offset or an
+ * env index that would reach 2^32 - 1. */
+int vnl_policy_decode(vnl_policy*, const float* params, const float* obs_mean, const float* obs_std,
+                      const float* latent, const float* obs, const float* eps_action, int32_t batch,
+                      int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
+                      const float* rand_action /* or NULL */, float* rand_log_prob /* or NULL */, void* stream);
+int vnl_policy_decode_noise(vnl_policy*, const float* params, const float* obs_mean, const float* obs_std,
+                            const float* latent /* NULL: z drawn, stream 0 */, const float* obs,
+                            const vnl_policy_noise*, int32_t batch, int32_t deterministic, float* action,
+                            float* raw_action, float* log_prob, float* logits, float* rand_log_prob /* or NULL */,
+                            void* stream);
+
 /* ---- rollout post-processing: the training wrappers and the Transition logging in ONE launch ----
  * brax EpisodeWrapper + AutoResetWrapper as applied by the reference's wrap_for_training
  * (ppo_imitation/train.py:204-214) and the per-step Transition of actor_step

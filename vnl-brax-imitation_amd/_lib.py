@@ -192,7 +192,7 @@ class BodyDomain(C.Structure):  # include/vnl.h: vnl_body_domain (float64 device
 EXPORTS = (
     "vnl_last_error", "vnl_version", "vnl_model_create", "vnl_model_destroy", "vnl_env_create", "vnl_env_destroy",
     "vnl_env_dims", "vnl_env_reset", "vnl_env_reset_done", "vnl_env_reset_done_weighted", "vnl_start_priority_update", "vnl_env_step", "vnl_env_step_post", "vnl_env_step_post_eval", "vnl_env_fk", "vnl_env_debug", "vnl_env_scratch", "vnl_policy_create", "vnl_policy_destroy",
-    "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_rollout_post", "vnl_rollout_eval", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
+    "vnl_policy_num_params", "vnl_policy_forward", "vnl_policy_forward_noise", "vnl_policy_decode", "vnl_policy_decode_noise", "vnl_rollout_post", "vnl_rollout_eval", "vnl_ppo_head", "vnl_adam_step", "vnl_gather_rows",
     "vnl_ppo_update_create", "vnl_ppo_update_destroy", "vnl_ppo_update_num_params", "vnl_ppo_update_buffer",
     "vnl_ppo_minibatch_grad",
     "vnl_ppo_minibatch_grad_part",
@@ -260,6 +260,14 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.vnl_policy_num_params.restype = C.c_int64
         lib.vnl_policy_forward.argtypes = [vp] + [vp] * 7 + [C.c_int32, C.c_int32] + [vp] * 6 + [vp, vp] + [vp]
         lib.vnl_policy_forward_noise.argtypes = [vp] + [vp] * 5 + [C.POINTER(PolicyNoise), C.c_int32, C.c_int32] + [vp] * 7 + [vp]
+        # (handle; params, obs_mean, obs_std, latent, obs, eps_action; batch, deterministic; action, raw_action, log_prob, logits;
+        #  rand_action, rand_log_prob; stream)
+        lib.vnl_policy_decode.argtypes = [vp] + [vp] * 6 + [C.c_int32, C.c_int32] + [vp] * 4 + [vp, vp] + [vp]
+        # (handle; params, obs_mean, obs_std, latent or NULL, obs; noise; batch, deterministic; action, raw_action, log_prob,
+        #  logits, rand_log_prob; stream)
+        lib.vnl_policy_decode_noise.argtypes = [vp] + [vp] * 5 + [C.POINTER(PolicyNoise), C.c_int32, C.c_int32] + [vp] * 5 + [vp]
+        if hasattr(lib, "vnl_policy_decode_threads_"):  # (the tile-shape knob of tools/decode_bench.py: not in include/vnl.h)
+            lib.vnl_policy_decode_threads_.argtypes = [vp, C.c_int32]
     return lib
 
 

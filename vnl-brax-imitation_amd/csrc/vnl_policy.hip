@@ -484,6 +484,121 @@ __global__ void __launch_bounds__(PTHREADS) vnl_policy_kernel_t(PolicyDev p, con
   POL_STAMP(21);
 }
 
+// Latent-driven acting: the motor decoder alone.  The arithmetic of the acting kernel above from "decoder input
+// [z | normalised obs] -> X" on, with z read from latent[batch][latent] (ZDRAW = false) or drawn here as stream 0's normal
+// draw, z ~ N(0, I): the prior of the KL term, on the counters the acting kernel uses for eps_latent (ZDRAW = true; recorded
+// through nz.eps_latent_out).  NDRAW: eps_action and the shared random action are streams 1 and 2 of vnl_policy_noise instead
+// of caller buffers.  A kernel of its own, not further MODEs of vnl_policy_kernel_t: the four instantiations above keep their
+// registers (csrc/libvnl.so.resources.txt).  No trajectory tile: two narrow activation buffers (p.ldA == p.ldB) and P, the
+// LDS shape of MODE 2; the thread count is the launch's (256 / 512 / 1024, vnl_policy_decode_threads_).  The distribution
+// tail is the acting kernel's, restated here so that not a line of that kernel changes.
+template <bool ZDRAW, bool NDRAW>
+__global__ void __launch_bounds__(PTHREADS) vnl_policy_decode_kernel_t(PolicyDev p, const float* __restrict__ params,
+                                                                     const float* __restrict__ obs_mean,
+                                                                     const float* __restrict__ obs_std,
+                                                                     const float* __restrict__ latent,
+                                                                     const float* __restrict__ obs,
+                                                                     const float* __restrict__ eps_action, int batch,
+                                                                     int deterministic, float* __restrict__ action,
+                                                                     float* __restrict__ raw_action, float* __restrict__ log_prob,
+                                                                     float* __restrict__ logits,
+                                                                     const float* __restrict__ rand_action,
+                                                                     float* __restrict__ rand_log_prob, PolicyNoiseDev nz) {
+  extern __shared__ __align__(16) float lds[];
+  float* X = lds;
+  float* Y = lds + PT * p.ldA;
+  float* P = Y + PT * p.ldB;  // K-slice partial sums of the Dense in flight; the draws between two Denses
+  const int e0 = blockIdx.x * PT, tid = threadIdx.x;
+  const int nrow = min(PT, batch - e0);
+  int ldx = p.ldA, ldy = p.ldB;
+  const int64_t step = (ZDRAW || NDRAW) ? *nz.step_base + nz.step_offset : 0;  // (read only)
+  // ---- decoder input [z | normalised obs] -> X (rows beyond the batch are zero)
+  if (ZDRAW) {  // stream 0 -> P[r][c] -> X
+    const int lat4 = (p.latent + 3) & ~3;
+    draw_normal_tile(nz, step, 0u, e0, nrow, p.latent, P, nz.eps_latent_out);
+    __syncthreads();
+    for (int i = tid; i < PT * p.latent; i += PNT) {
+      const int r = i / p.latent, c = i - r * p.latent;
+      X[r * ldx + c] = r < nrow ? P[r * lat4 + c] : 0.f;
+    }
+  } else {
+    load_tile(latent + (size_t)e0 * p.latent, nrow, p.latent, X, ldx, nullptr, nullptr);
+  }
+  load_tile(obs + (size_t)e0 * p.obs_size, nrow, p.obs_size, X + p.latent, ldx, obs_mean, obs_std);
+  __syncthreads();
+  // ---- decoder (ipn:56-70): [Dense -> ReLU -> LayerNorm] x (n-1), last Dense linear
+  int K = p.latent + p.obs_size;
+  for (int l = 0; l < p.n_dec; l++) {
+    const bool last = l == p.n_dec - 1;
+    dense_tile(X, ldx, K, params, p.dec_w[l], p.dec_b[l], p.dec[l], Y, ldy, !last, P);
+    if (!last) {
+      layer_norm_rows<false>(Y, ldy, p.dec[l], params + p.dec_g[l], params + p.dec_be[l]);
+      __syncthreads();
+    }
+    float* t = X;
+    X = Y, Y = t;
+    int tl = ldx;
+    ldx = ldy, ldy = tl;
+    K = p.dec[l];
+  }
+  // ---- distribution (brax NormalTanhDistribution; ppo_networks.py:56-83): X holds logits [loc | s]
+  const int na = p.act_size;
+  for (int i = tid; i < PT * 2 * na; i += PNT) {
+    int r = i / (2 * na), c = i - r * 2 * na;
+    if (r < nrow) logits[(size_t)(e0 + r) * 2 * na + c] = X[r * ldx + c];
+  }
+  float* lp = Y;  // per-(env, action) log-prob terms
+  const bool has_rand = NDRAW ? rand_log_prob != nullptr : rand_action != nullptr;
+  const int act4 = (na + 3) & ~3;
+  if (NDRAW && !deterministic) {  // stream 1 -> P[r][c]; stream 2, ONE draw shared by the batch -> P[PT][c], the same in every workgroup
+    draw_normal_tile(nz, step, 1u, e0, nrow, na, P, nz.eps_action_out);
+    if (has_rand && tid < (act4 >> 2)) {
+      uint32_t x[4];
+      philox4x32_10((uint32_t)tid, 0xFFFFFFFFu, (uint32_t)step, ((uint32_t)(step >> 32) << 2) | 2u, nz.key0, nz.key1, x);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const float v = (float)((int)(2u * (x[q] >> 8) + 1u) - (1 << 24)) * 0x1p-24f;  // (as in the acting kernel)
+        P[PT * act4 + 4 * tid + q] = v;
+        if (blockIdx.x == 0 && nz.rand_action_out && 4 * tid + q < na) nz.rand_action_out[4 * tid + q] = v;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < PT * na; i += PNT) {
+    int r = i / na, c = i - r * na;
+    float term = 0.f;
+    if (r < nrow) {
+      size_t g = (size_t)(e0 + r) * na + c;
+      float loc = X[r * ldx + c];
+      if (deterministic) {
+        action[g] = tanhf(loc);  // mode()
+      } else {
+        float scale = softplusf(X[r * ldx + na + c]) + 0.001f;
+        float eps = NDRAW ? P[r * act4 + c] : eps_action[g];
+        float raw = loc + scale * eps;
+        raw_action[g] = raw, action[g] = tanhf(raw);
+        term = -0.5f * eps * eps - 0.9189385332046727f - logf(scale) - 2.f * (0.6931471805599453f - raw - softplusf(-2.f * raw));
+        if (has_rand) {
+          float x = NDRAW ? P[PT * act4 + c] : rand_action[c], z = (x - loc) / scale;
+          lp[r * ldy + na + c] = -0.5f * z * z - 0.9189385332046727f - logf(scale) - 2.f * (0.6931471805599453f - x - softplusf(-2.f * x));
+        }
+      }
+    }
+    lp[r * ldy + c] = term;
+  }
+  __syncthreads();
+  if (!deterministic && tid < nrow) {
+    float s = 0.f;
+    for (int c = 0; c < na; c++) s += lp[tid * ldy + c];
+    log_prob[e0 + tid] = s;
+    if (has_rand) {
+      float s2 = 0.f;
+      for (int c = 0; c < na; c++) s2 += lp[tid * ldy + na + c];
+      rand_log_prob[e0 + tid] = s2;
+    }
+  }
+}
+
 // ----------------------------------------------------------------------------- host side
 void vnl_set_error_(const char* msg);  // vnl_lib.hip: feeds vnl_last_error()
 static int pfail(int code, const char* msg) {
@@ -499,6 +614,9 @@ struct vnl_policy {
   PolicyDev d2;       // MODE 2 (training form from the first Dense output on): no trajectory tile, both activation buffers narrow
   size_t lds_bytes2;
   int threads2;
+  PolicyDev d3;       // the decode kernels: two buffers as wide as the widest decoder activation, P for the decoder's Denses alone
+  size_t lds_bytes3;
+  int threads3;
 };
 
 // threads of the MODE 2 launch (256 / 512 / 1024) and the LDS it then needs: the partial-sum buffer shrinks with the wave count
@@ -521,6 +639,40 @@ int vnl_policy_set_threads2_(vnl_policy* p, int threads) {
   if (!ok2) return VNL_ERR_UNSUPPORTED;
   p->threads2 = threads;
   p->lds_bytes2 = (size_t)PT * (2 * d.ldB + pw2) * sizeof(float);
+  return VNL_OK;
+}
+
+// Default thread count of the decode kernels (profiles/latent_policy_bench.txt holds the comparison)
+#define PDECODE_THREADS 1024
+
+// Threads of the decode launches (256 / 512 / 1024) and the LDS they then need.  Not part of include/vnl.h: the knob
+// tools/decode_bench.py turns to compare the candidates; the product launches with PDECODE_THREADS.
+extern "C" int vnl_policy_decode_threads_(vnl_policy* p, int32_t threads) {
+  if (!p || (threads != 256 && threads != 512 && threads != 1024)) return pfail(VNL_ERR_ARG, "vnl_policy_decode_threads_: 256, 512 or 1024");
+  const PolicyDev& d = p->d3;
+  const int lat4 = (d.latent + 3) & ~3, act4 = (d.act_size + 3) & ~3;
+  // P holds the K-slice partial sums of a decoder Dense, and between two Denses the draws: [PT][lat4], then [PT + 1][act4]
+  int pw = lat4 > 2 * act4 ? lat4 : 2 * act4;
+  for (int l = 0; l < d.n_dec; l++) {
+    const int n = d.dec[l];
+    int G = (n + 63) / 64, Gp = 1;
+    while (Gp < G && Gp < threads / 64) Gp <<= 1;
+    if (G > Gp) return pfail(VNL_ERR_UNSUPPORTED, "decoder layer too wide for this thread count");
+    const int w = (threads / 64 / Gp) * ((n + 3) & ~3);
+    pw = w > pw ? w : pw;
+  }
+  const size_t lds = (size_t)PT * (d.ldA + d.ldB + pw) * sizeof(float);
+  if (lds > 160 * 1024 - 512) return pfail(VNL_ERR_UNSUPPORTED, "decoder too wide for the 16-env LDS tile");
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)vnl_policy_decode_kernel_t<false, false>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)vnl_policy_decode_kernel_t<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)vnl_policy_decode_kernel_t<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
+  }
+  p->threads3 = threads, p->lds_bytes3 = lds;
   return VNL_OK;
 }
 
@@ -616,6 +768,16 @@ extern "C" int vnl_policy_create(const vnl_policy_spec* s, int32_t max_batch, in
   }
   p->d2 = d, p->d2.ldA = d.ldB;
   (void)vnl_policy_set_threads2_(p, PTHREADS);
+  {  // decode kernels: no trajectory tile, no encoder; both buffers hold [z | obs] or a decoder activation
+    int w3 = d.latent + d.obs_size;
+    for (int l = 0; l < d.n_dec; l++) w3 = d.dec[l] > w3 ? d.dec[l] : w3;
+    p->d3 = d, p->d3.ldA = p->d3.ldB = pad(w3);
+    const int rc = vnl_policy_decode_threads_(p, PDECODE_THREADS);
+    if (rc != VNL_OK) {
+      delete p;
+      return rc;
+    }
+  }
   p->device = device, p->max_batch = max_batch;
   if (p->lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)vnl_policy_kernel_t<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -688,6 +850,64 @@ extern "C" int vnl_policy_forward_noise(vnl_policy* p, const float* params, cons
                      obs_mean, obs_std, traj, obs, (const float*)nullptr, (const float*)nullptr, (int)batch, (int)deterministic,
                      action, raw_action, log_prob, logits, latent_mean, latent_logvar, (const float*)nullptr, rand_log_prob,
                      PolicyTrainOut{}, nz);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
+  return VNL_OK;
+}
+
+// The decoder alone (vnl_policy_decode_kernel_t): z from the caller, noise from the caller
+extern "C" int vnl_policy_decode(vnl_policy* p, const float* params, const float* obs_mean, const float* obs_std,
+                                 const float* latent, const float* obs, const float* eps_action, int32_t batch,
+                                 int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
+                                 const float* rand_action, float* rand_log_prob, void* stream) {
+  if (!p || !params || !obs || !action || !logits) return pfail(VNL_ERR_ARG, "vnl_policy_decode: null argument");
+  if (!latent) return pfail(VNL_ERR_ARG, "vnl_policy_decode: latent is null (vnl_policy_decode_noise draws it from the prior)");
+  if (!deterministic && (!eps_action || !raw_action || !log_prob))
+    return pfail(VNL_ERR_ARG, "vnl_policy_decode: stochastic mode needs eps_action, raw_action, log_prob");
+  if ((rand_action == nullptr) != (rand_log_prob == nullptr) || (rand_action && deterministic))
+    return pfail(VNL_ERR_ARG, "rand_action / rand_log_prob: both or neither, stochastic mode only");
+  if ((obs_mean == nullptr) != (obs_std == nullptr)) return pfail(VNL_ERR_ARG, "obs_mean / obs_std must both be given or both null");
+  if (batch <= 0 || batch > p->max_batch) return pfail(VNL_ERR_ARG, "batch out of range");
+  const int grid = (batch + PT - 1) / PT;
+  hipLaunchKernelGGL((vnl_policy_decode_kernel_t<false, false>), dim3(grid), dim3(p->threads3), p->lds_bytes3, (hipStream_t)stream,
+                     p->d3, params, obs_mean, obs_std, latent, obs, eps_action, (int)batch, (int)deterministic, action, raw_action,
+                     log_prob, logits, rand_action, rand_log_prob, PolicyNoiseDev{});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
+  return VNL_OK;
+}
+
+// .. with the noise drawn in the kernel: streams 1 and 2 of vnl_policy_noise, and with a null latent z itself as stream 0
+extern "C" int vnl_policy_decode_noise(vnl_policy* p, const float* params, const float* obs_mean, const float* obs_std,
+                                       const float* latent, const float* obs, const vnl_policy_noise* noise, int32_t batch,
+                                       int32_t deterministic, float* action, float* raw_action, float* log_prob, float* logits,
+                                       float* rand_log_prob, void* stream) {
+  if (!p || !params || !obs || !noise || !action || !logits) return pfail(VNL_ERR_ARG, "vnl_policy_decode_noise: null argument");
+  if (!deterministic && (!raw_action || !log_prob))
+    return pfail(VNL_ERR_ARG, "vnl_policy_decode_noise: stochastic mode needs raw_action, log_prob");
+  if (rand_log_prob && deterministic) return pfail(VNL_ERR_ARG, "rand_log_prob: stochastic mode only");
+  if ((obs_mean == nullptr) != (obs_std == nullptr)) return pfail(VNL_ERR_ARG, "obs_mean / obs_std must both be given or both null");
+  if (batch <= 0 || batch > p->max_batch) return pfail(VNL_ERR_ARG, "batch out of range");
+  if (!noise->step_base) return pfail(VNL_ERR_ARG, "vnl_policy_noise: step_base is null (a device pointer to the step counter)");
+  if (noise->step_offset < 0 || noise->env_offset < 0)
+    return pfail(VNL_ERR_ARG, "vnl_policy_noise: step_offset and env_offset must not be negative");
+  if (noise->env_offset + (int64_t)batch >= 0xFFFFFFFFll)
+    return pfail(VNL_ERR_ARG, "vnl_policy_noise: env_offset + batch must stay below 2^32 - 1 (that env index is the shared draw's)");
+  PolicyNoiseDev nz{};
+  nz.key0 = (uint32_t)noise->seed, nz.key1 = (uint32_t)(noise->seed >> 32);
+  nz.step_base = noise->step_base, nz.step_offset = noise->step_offset, nz.env0 = (uint32_t)noise->env_offset;
+  nz.eps_latent_out = latent ? nullptr : noise->eps_latent_out;  // (a given latent: stream 0 is not drawn, nothing to record)
+  nz.eps_action_out = deterministic ? nullptr : noise->eps_action_out;
+  nz.rand_action_out = deterministic ? nullptr : noise->rand_action_out;
+  const int grid = (batch + PT - 1) / PT;
+  if (latent)
+    hipLaunchKernelGGL((vnl_policy_decode_kernel_t<false, true>), dim3(grid), dim3(p->threads3), p->lds_bytes3, (hipStream_t)stream,
+                       p->d3, params, obs_mean, obs_std, latent, obs, (const float*)nullptr, (int)batch, (int)deterministic, action,
+                       raw_action, log_prob, logits, (const float*)nullptr, rand_log_prob, nz);
+  else
+    hipLaunchKernelGGL((vnl_policy_decode_kernel_t<true, true>), dim3(grid), dim3(p->threads3), p->lds_bytes3, (hipStream_t)stream,
+                       p->d3, params, obs_mean, obs_std, (const float*)nullptr, obs, (const float*)nullptr, (int)batch,
+                       (int)deterministic, action, raw_action, log_prob, logits, (const float*)nullptr, rand_log_prob, nz);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return pfail(VNL_ERR_HIP, hipGetErrorString(e));
   return VNL_OK;

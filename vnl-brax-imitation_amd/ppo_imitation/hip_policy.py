@@ -128,3 +128,100 @@ class HipIntentionPolicy:
         if rlp is not None:
             extras["rand_log_prob"] = rlp
         return action, {**extras, "latent_mean": lat_mean, "latent_logvar": lat_logvar}
+
+    @torch.no_grad()
+    def decode(self, params: torch.Tensor, obs_mean: Optional[torch.Tensor], obs_std: Optional[torch.Tensor],
+               latent: torch.Tensor, obs: torch.Tensor, eps_action: Optional[torch.Tensor], deterministic: bool = False,
+               rand_action: Optional[torch.Tensor] = None, out: Optional[dict] = None) -> Tuple[torch.Tensor, dict]:
+        """vnl_policy_decode: the decoder alone on a caller-supplied latent [B, latent] -- the arithmetic of `forward` from
+        the decoder input [z | normalised obs] on.  `out` as in `forward_noise`."""
+        B, na, nl = obs.shape[0], self.action_size, self.net.latents
+        c = lambda t: t.contiguous()  # noqa: E731
+        if latent is None:
+            raise ValueError("decode needs a latent; decode_noise(latent=None) draws it from the prior")
+        if tuple(latent.shape) != (B, nl) or latent.dtype != torch.float32 or latent.device != obs.device:
+            raise ValueError(f"latent must be a float32 {(B, nl)} tensor on the inputs' device")
+        latent, obs, params = c(latent), c(obs), c(params)
+        stochastic = not deterministic
+        buf = self._out_buffers(out, obs.device)
+        action, logits = buf("action", (B, na)), buf("logits", (B, 2 * na))
+        raw, lp = buf("raw_action", (B, na), stochastic), buf("log_prob", (B,), stochastic)
+        rlp = buf("rand_log_prob", (B,), stochastic and rand_action is not None)
+        rand_action = c(rand_action) if rlp is not None else None
+        eps_action = c(eps_action) if stochastic else None
+        if obs_mean is not None:
+            obs_mean, obs_std = c(obs_mean), c(obs_std)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        _lib.check(self.lib, self.lib.vnl_policy_decode(
+            self.h, p(params), p(obs_mean), p(obs_std), p(latent), p(obs), p(eps_action), B, int(deterministic), p(action),
+            p(raw), p(lp), p(logits), p(rand_action), p(rlp), stream))
+        self._hold = (latent, obs, eps_action, params, obs_mean, obs_std, rand_action)
+        extras = {} if deterministic else {"log_prob": lp, "raw_action": raw}
+        if rlp is not None:
+            extras["rand_log_prob"] = rlp
+        return action, {**extras, "logits": logits}
+
+    @torch.no_grad()
+    def decode_noise(self, params: torch.Tensor, obs_mean: Optional[torch.Tensor], obs_std: Optional[torch.Tensor],
+                     latent: Optional[torch.Tensor], obs: torch.Tensor, counter: torch.Tensor, step_offset: int = 0,
+                     seed: int = 0, env_offset: int = 0, deterministic: bool = False, rand: bool = True,
+                     out: Optional[dict] = None, eps_out: Optional[dict] = None) -> Tuple[torch.Tensor, dict]:
+        """vnl_policy_decode_noise: the decoder alone, eps_action and the shared random action drawn by the kernel from
+        streams 1 and 2 keyed by (seed, *counter + step_offset, env_offset + row), as `forward_noise` draws them.
+        `latent=None` selects the prior draw: z is stream 0's normal draw, recorded in eps_out["eps_latent"] when given (with
+        a latent given, stream 0 is not drawn and that record is left alone).  `counter`, `out`, `eps_out`, `rand` as in
+        `forward_noise`."""
+        B, na, nl = obs.shape[0], self.action_size, self.net.latents
+        c = lambda t: t.contiguous()  # noqa: E731
+        obs, params = c(obs), c(params)
+        if latent is not None:
+            if tuple(latent.shape) != (B, nl) or latent.dtype != torch.float32 or latent.device != obs.device:
+                raise ValueError(f"latent must be a float32 {(B, nl)} tensor on the inputs' device")
+            latent = c(latent)
+        if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != obs.device:
+            raise ValueError("counter must be an int64 tensor of one element on the inputs' device")
+        eps_out = eps_out or {}
+        stochastic = not deterministic
+        buf = self._out_buffers(out, obs.device)
+        action, logits = buf("action", (B, na)), buf("logits", (B, 2 * na))
+        raw, lp = buf("raw_action", (B, na), stochastic), buf("log_prob", (B,), stochastic)
+        rlp = buf("rand_log_prob", (B,), stochastic and rand)
+        rec = {k: eps_out.get(k) for k in ("eps_latent", "eps_action", "rand_action")}
+        for k, shape in (("eps_latent", (B, nl)), ("eps_action", (B, na)), ("rand_action", (na,))):
+            t = rec[k]
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"eps_out[{k!r}] must be a contiguous float32 {shape} tensor")
+        if obs_mean is not None:
+            obs_mean, obs_std = c(obs_mean), c(obs_std)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        nz = _lib.PolicyNoise()
+        nz.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        nz.step_base, nz.step_offset, nz.env_offset = p(counter), int(step_offset), int(env_offset)
+        nz.eps_latent_out, nz.eps_action_out, nz.rand_action_out = p(rec["eps_latent"]), p(rec["eps_action"]), p(rec["rand_action"])
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        _lib.check(self.lib, self.lib.vnl_policy_decode_noise(
+            self.h, p(params), p(obs_mean), p(obs_std), p(latent), p(obs), C.byref(nz), B, int(deterministic), p(action), p(raw),
+            p(lp), p(logits), p(rlp), stream))
+        self._hold = (latent, obs, params, obs_mean, obs_std, counter, rec)
+        extras = {} if deterministic else {"log_prob": lp, "raw_action": raw}
+        if rlp is not None:
+            extras["rand_log_prob"] = rlp
+        return action, {**extras, "logits": logits}
+
+    @staticmethod
+    def _out_buffers(out: Optional[dict], device):
+        """buf(name, shape, wanted=True): out[name] when given (checked), else a fresh float32 tensor; None if not wanted"""
+        out = out or {}
+
+        def buf(name, shape, wanted=True):
+            if not wanted:
+                return None
+            t = out.get(name)
+            if t is None:
+                return torch.empty(shape, dtype=torch.float32, device=device)
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
+                raise ValueError(f"out[{name!r}] must be a contiguous float32 {shape} tensor on the inputs' device")
+            return t
+
+        return buf

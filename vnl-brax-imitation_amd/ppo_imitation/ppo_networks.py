@@ -278,3 +278,146 @@ def make_inference_fn(ppo_networks: PPOImitationNetworks):
         return policy
 
     return make_policy
+
+
+class _DecoderPolicy:
+    """make_decoder_inference_fn(...)(params, latent=...): latent-driven acting, the motor decoder alone as a policy.
+
+    Duck-types `_DeviceNoisePolicy` (noise == "device", `.counter`, `.deterministic`, the same call), so the unrolls, the
+    graph captures and the evaluator of acting.py take it as they are.  `trajectories` is read only by a callable latent."""
+
+    noise = "device"
+
+    def __init__(self, nets: PPOImitationNetworks, hip_cache: dict, params, latent, deterministic: bool, use_hip: bool,
+                 seed: int, env_offset: int, counter: Optional[torch.Tensor], latent_out: Optional[torch.Tensor]):
+        self.nets, self.hip_cache, self.params = nets, hip_cache, params
+        self.deterministic, self.use_hip = bool(deterministic), use_hip
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        if self.env_offset < 0:
+            raise ValueError("env_offset must not be negative")
+        nl = nets.policy_module.latents
+        if isinstance(latent, str):
+            if latent != "prior":
+                raise ValueError(f"latent must be 'prior', a float32 [B, {nl}] tensor or a callable (traj, obs) -> latent, got {latent!r}")
+        elif isinstance(latent, torch.Tensor):
+            self._check_latent(latent, None, "latent")
+        elif not callable(latent):
+            raise ValueError(f"latent must be 'prior', a float32 [B, {nl}] tensor or a callable (traj, obs) -> latent")
+        if latent_out is not None:
+            self._check_latent(latent_out, None, "latent_out")
+        self.latent, self.latent_out = latent, latent_out
+        dev = params[1].device
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != dev:
+            raise ValueError("counter must be an int64 tensor of one element on the parameters' device")
+        self.counter = counter
+
+    def _check_latent(self, z, B, what):
+        nl = self.nets.policy_module.latents
+        if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] != nl or (B is not None and z.shape[0] != B):
+            raise ValueError(f"{what} must have shape [{'B' if B is None else B}, {nl}], got "
+                             f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__}")
+        if z.dtype != torch.float32:
+            raise ValueError(f"{what} must be float32, got {z.dtype}")
+
+    @torch.no_grad()
+    def __call__(self, trajectories: torch.Tensor, observations: torch.Tensor, key_sample=None, *, step_offset: int = 0,
+                 advance: bool = True, out: Optional[dict] = None) -> Tuple[torch.Tensor, dict]:
+        if observations.dim() != 2:
+            raise ValueError("the draws are keyed by the row: observations must be (batch, obs_size)")
+        B = observations.shape[0]
+        z = None  # the prior draw, made by the backend
+        if callable(self.latent):  # a high-level controller of torch ops, in front of the decode launch
+            z = self.latent(trajectories, observations)
+            self._check_latent(z, B, "the latent callable's result")
+        elif isinstance(self.latent, torch.Tensor):  # read live: the caller may rewrite it in place between calls
+            z = self.latent
+            self._check_latent(z, B, "latent")
+        if self.latent_out is not None:
+            self._check_latent(self.latent_out, B, "latent_out")
+            if z is not None:
+                self.latent_out.copy_(z)
+        res = (self._hip if self.use_hip else self._torch)(z, observations, int(step_offset), out)
+        if advance:
+            self.counter.add_(1)
+        return res
+
+    def _hip(self, z, observations, step_offset, out):
+        from .hip_policy import HipIntentionPolicy
+
+        nets, dist = self.nets, self.nets.parametric_action_distribution
+        normalizer_params, policy_params = self.params
+        dev, B = observations.device, observations.shape[0]
+        k = (dev, B)
+        if k not in self.hip_cache:
+            self.hip_cache[k] = HipIntentionPolicy(nets.policy_module, dist.event_size, B, dev)
+        mean = std = None
+        if nets.normalizes and normalizer_params is not None:
+            mean, std = normalizer_params.mean, normalizer_params.std
+        eps_out = None
+        if z is None and self.latent_out is not None:  # the kernel writes the z it draws
+            if not self.latent_out.is_contiguous() or self.latent_out.device != dev:
+                raise ValueError("latent_out must be contiguous and on the inputs' device")
+            eps_out = {"eps_latent": self.latent_out}
+        action, extras = self.hip_cache[k].decode_noise(
+            policy_params.detach(), mean, std, z, observations, self.counter, step_offset=step_offset, seed=self.seed,
+            env_offset=self.env_offset, deterministic=self.deterministic, out=out, eps_out=eps_out)
+        if self.deterministic:
+            return action, {}
+        return action, {k2: extras[k2] for k2 in _LOGGED}
+
+    def _torch(self, z, observations, step_offset, out):
+        nets, dist = self.nets, self.nets.parametric_action_distribution
+        normalizer_params, policy_params = self.params
+        dev, B = observations.device, observations.shape[0]
+        if self.env_offset + B >= philox.SHARED_ENV:
+            raise ValueError("env_offset + batch must stay below 2^32 - 1")
+        step = self.counter.to(dev) + step_offset
+        env = self.env_offset + torch.arange(B, dtype=torch.int64, device=dev)
+        if z is None:  # the prior of the KL term, on the counters of the acting policy's eps_latent
+            z = philox.normal(self.seed, step, env, nets.policy_module.latents, philox.STREAM_LATENT)
+            if self.latent_out is not None:
+                self.latent_out.copy_(z)
+        obs = running_statistics.normalize(observations, normalizer_params) if nets.normalizes else observations
+        logits = nets.policy_module.decode(policy_params, torch.cat([z, obs], dim=-1))
+        if self.deterministic:
+            res = {"action": dist.mode(logits)}
+        else:
+            eps_action = philox.normal(self.seed, step, env, dist.event_size, philox.STREAM_ACTION)
+            raw_actions = dist.sample_no_postprocessing(logits, eps_action)
+            random_actions = philox.shared_uniform(self.seed, step, dist.event_size, device=dev)
+            res = {"action": dist.postprocess(raw_actions), "log_prob": dist.log_prob(logits, raw_actions),
+                   "rand_log_prob": dist.log_prob(logits, random_actions.expand_as(raw_actions)),
+                   "raw_action": raw_actions, "logits": logits}
+        if out is not None:
+            res = {k2: out[k2].copy_(v) for k2, v in res.items()}
+        return res["action"], {k2: res[k2] for k2 in _LOGGED if k2 in res}
+
+
+def make_decoder_inference_fn(ppo_networks: PPOImitationNetworks):
+    """Latent-driven acting: the intention network's decoder alone, [z | normalised obs] -> action, as a policy (the
+    encoder is not run and its parameters are not read).  Needs the running-statistics normaliser or the identity as the
+    observation preprocessor."""
+    if not ppo_networks.hip_ok:
+        raise ValueError("the decoder policy needs running_statistics.normalize or the identity as the observation preprocessor")
+    hip_cache = {}
+
+    def make_decoder_policy(params, latent="prior", deterministic: bool = False, backend: str = "auto", seed: int = 0,
+                            env_offset: int = 0, counter: Optional[torch.Tensor] = None,
+                            latent_out: Optional[torch.Tensor] = None):
+        """latent: "prior" = z ~ N(0, I) drawn per env and step, stream 0 of the counter-based noise (philox.py), keyed by
+        (seed, step, env_offset + row); a float32 [B, latent] tensor, read live at every call (rewrite it in place between
+        steps, also between replays of a captured graph); or a callable (traj, obs) -> [B, latent] of torch ops, which runs
+        in front of the decode launch.  eps_action and the shared random action are streams 1 and 2, as with
+        make_inference_fn(...)(params, noise="device"); `counter`, `seed`, `env_offset` and the returned policy's call are
+        that policy's.  backend: "hip" = vnl_policy_decode_noise, "torch" = IntentionNetwork.decode on the restated draws,
+        "auto" = hip when the parameters live on a HIP device.  latent_out: a float32 [B, latent] tensor that every call
+        overwrites with the z it used (in prior mode on the hip backend the kernel writes it)."""
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError(f"backend must be 'auto', 'hip' or 'torch', got {backend!r}")
+        use_hip = backend == "hip" or (backend == "auto" and params[1].is_cuda and ppo_networks.hip_ok)
+        return _DecoderPolicy(ppo_networks, hip_cache, params, latent, deterministic, use_hip, seed, env_offset, counter,
+                              latent_out)
+
+    return make_decoder_policy
