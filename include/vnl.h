@@ -534,6 +534,42 @@ int vnl_rollout_eval(const vnl_eval_desc*, int32_t num_envs, void* stream);
 int vnl_env_step_post_eval(vnl_env*, const float* action, const vnl_state* state, const vnl_post_desc* desc,
                            const vnl_eval_desc* eval, void* stream);
 
+/* ---- recorded rollouts: per-step traces of chosen envs, one row per call ----
+ * What the reference's policy_params_fn keeps of an episode it watches (train.py:154-331: qpos, termination_error, reward, the
+ * logits, log_prob, rand_log_prob per step, and [reference qpos | rollout qpos] for the renderer, train.py:289-291), written on
+ * the device by a launch of its own after the step (and after vnl_rollout_post / vnl_rollout_eval, before a fresh reset).
+ * Per recorder r, with e = env_index ? env_index[r] : r:
+ *   nothing is written if e is outside [0, num_envs), if open[r] == 0, or if c = count[r] >= capacity
+ *   rows[r][c] = { reference pose | col 0 | col 1 | .. }
+ *     reference pose (only with ref_frame / ref_clip): nq words -- position, quaternion and joints of clip ref_clip[e] at frame
+ *       clamp(ref_frame[e], 0, T - 1), from the env's own device copy of the clip (a clip index outside [0, num_clips) is
+ *       clamped likewise: never indexed)
+ *     col k: `width` 32-bit words of src[e] (row e of [num_envs][width]), moved bit-exactly: float32, int32, NaN payloads;
+ *       a column whose src is NULL is `width` words 0x7FC00000 (a quiet NaN: row 0, the reset state, has no policy outputs)
+ *   count[r] = c + 1
+ *   if stop_at_done and done is given and done[e] != 0: open[r] = 0
+ * Rows at or beyond count[r] are never touched; two recorders may watch the same env.  The caller sets count = 0 and
+ * open = 1.  rows, count and open must not be a column's source.  The descriptor is copied into the launch's arguments
+ * (capturable in a hipGraph: the cursor lives on the device, so replays advance it; it need not outlive the call).
+ * VNL_ERR_ARG (nothing launched, the field named) for a null env, desc, rows, count or open, num_rec < 1, capacity < 1,
+ * num_cols outside 0..VNL_RECORD_MAX_COLS, a width < 1, ref_frame given without ref_clip or the other way round, and
+ * row_width != (ref ? nq : 0) + the sum of the widths. */
+#define VNL_RECORD_MAX_COLS 16
+typedef struct vnl_record_col {
+  const void* src;
+  int32_t width, pad_;
+} vnl_record_col;
+typedef struct vnl_record_desc {
+  const int32_t* env_index;            /* device [num_rec], or NULL: recorder r watches env r */
+  const float* done;                   /* [num_envs] the wrapper's done, or NULL */
+  const int32_t *ref_frame, *ref_clip; /* [num_envs], both or none: the row starts with the clip's pose */
+  int32_t *count, *open;               /* [num_rec]; the caller sets count = 0 and open = 1 */
+  float* rows;                         /* [num_rec][capacity][row_width] */
+  int32_t num_rec, capacity, row_width, stop_at_done, num_cols, pad_;
+  vnl_record_col cols[VNL_RECORD_MAX_COLS];
+} vnl_record_desc;
+int vnl_env_record(vnl_env*, const vnl_record_desc*, void* stream);
+
 /* ---- PPO loss head: everything of compute_ppo_intention_loss after the network forward passes ----
  * (reference ppo_imitation/intention_losses.py:26-87 compute_gae, :131-202 loss) in three small launches: GAE,
  * advantage normalisation, tanh-Normal log-prob and entropy, clipped surrogate, value loss, latent KL,

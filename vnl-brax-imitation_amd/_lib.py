@@ -131,6 +131,19 @@ class EvalDesc(C.Structure):  # include/vnl.h: vnl_eval_desc
                [("episodes_per_env", C.c_int32), ("pad_", C.c_int32)]
 
 
+RECORD_MAX_COLS = 16  # include/vnl.h: VNL_RECORD_MAX_COLS
+
+
+class RecordCol(C.Structure):  # include/vnl.h: vnl_record_col
+    _fields_ = [("src", C.c_void_p), ("width", C.c_int32), ("pad_", C.c_int32)]
+
+
+class RecordDesc(C.Structure):  # include/vnl.h: vnl_record_desc
+    _fields_ = [(n, C.c_void_p) for n in ("env_index", "done", "ref_frame", "ref_clip", "count", "open", "rows")] + \
+               [(n, C.c_int32) for n in ("num_rec", "capacity", "row_width", "stop_at_done", "num_cols", "pad_")] + \
+               [("cols", RecordCol * RECORD_MAX_COLS)]
+
+
 class GatherOp(C.Structure):  # include/vnl.h: vnl_gather_op
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("T", C.c_int32), ("width", C.c_int32)]
 
@@ -199,6 +212,7 @@ EXPORTS = (
     "vnl_env_set_domain", "vnl_env_set_body_domain", "vnl_env_set_domain_ranges", "vnl_env_redraw_domain",
     "vnl_env_set_body_domain_ranges",
     "vnl_prediction_corr_plan", "vnl_prediction_corr",
+    "vnl_env_record",
 )
 _HIP_ONLY = ("vnl_policy_", "vnl_ppo_update_", "vnl_ppo_minibatch_", "vnl_prediction_corr")  # not in the test-only host simulation
 
@@ -229,6 +243,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "vnl_env_step_post_eval"):
         lib.vnl_env_step_post_eval.argtypes = [vp, vp, C.POINTER(StatePtrs), C.POINTER(PostDesc), C.POINTER(EvalDesc), vp]
         lib.vnl_rollout_eval.argtypes = [C.POINTER(EvalDesc), C.c_int32, vp]
+    lib.vnl_env_record.argtypes = [vp, C.POINTER(RecordDesc), vp]
     lib.vnl_env_fk.argtypes = [vp, vp, C.POINTER(StatePtrs), vp]
     lib.vnl_env_debug.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.vnl_env_scratch.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int32)]

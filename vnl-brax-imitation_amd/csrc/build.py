@@ -8,8 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (vnl_domain.hip last: the randomised env kernels, a translation unit of their own -- vnl_env_set_domain -- listed after the
 # existing kernels in the resource report; vnl_eval.hip: the step kernels that score an evaluation, vnl_env_step_post_eval,
-# apart for the same reason)
-SOURCES = ["vnl_lib.hip", "vnl_policy.hip", "vnl_ppo.hip", "vnl_domain.hip", "vnl_eval.hip"]
+# apart for the same reason; vnl_record.hip last: the kernel and entry of the recorded rollouts, vnl_env_record, likewise)
+SOURCES = ["vnl_lib.hip", "vnl_policy.hip", "vnl_ppo.hip", "vnl_domain.hip", "vnl_eval.hip", "vnl_record.hip"]
 DEPS = SOURCES + ["vnl_env_kernels.h", "vnl_body.h", "vnl_types.h", "vnl_inertial.h", "vnl_philox.h", "vnl_policy_train.h", "../../include/vnl.h"]
 OUT = os.path.join(HERE, "libvnl.so")
 

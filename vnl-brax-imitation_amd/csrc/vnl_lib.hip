@@ -2202,8 +2202,15 @@ extern "C" int vnl_start_priority_update(uint32_t* ended, uint32_t* failed, uint
 
 // the policy-forward entry points (vnl_policy_*) live in vnl_policy.hip
 
+// What csrc/vnl_record.hip (vnl_env_record: a translation unit of its own) reads of an env, whose struct is private to this
+// file: host code only, no kernel of this unit changes with it.
+void vnl_env_record_view_(const vnl_env* env, int* device, int* num_envs, int* nq, DevEnv* ev) {
+  *device = env->device, *num_envs = env->B, *nq = env->dm.nq, *ev = env->de;
+}
+
 #ifdef VNL_FORKJOIN_DEFINED
 // host simulation (tests/hostsim): this file is its one translation unit, so the randomised instantiations come in here
 #include "vnl_domain.hip"
 #include "vnl_eval.hip"
+#include "vnl_record.hip"
 #endif

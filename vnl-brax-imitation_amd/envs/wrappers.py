@@ -191,6 +191,12 @@ class EvalWrapper(Wrapper):
         if int(episodes_per_env) < 1:
             raise ValueError("episodes_per_env must be at least 1")
         self.episodes_per_env = int(episodes_per_env)
+        self.after_score = None  # a RolloutRecorder's row, for the length of an unroll: after the scoring, before a fresh reset
+
+    def _score_step(self, state: State) -> None:
+        self.score(state)
+        if self.after_score is not None:
+            self.after_score(state)
 
     def reset(self, rng=None, **kw) -> State:
         state = self.env.reset(rng, **kw)
@@ -259,14 +265,14 @@ class EvalWrapper(Wrapper):
         em: EvalMetrics = state.info["eval_metrics"]
         ar = self._fresh()
         if ar is not None:
-            ar.before_reset = self.score
+            ar.before_reset = self._score_step
         try:
             nstate = self.env.step(state, action)
         finally:
             if ar is not None:
                 ar.before_reset = None
         if ar is None:
-            self.score(nstate)
+            self._score_step(nstate)
         active = em.active_episodes
         em.episode_steps.copy_(torch.where(active.bool(), nstate.info["steps"], em.episode_steps))
         for k, acc in em.episode_metrics.items():

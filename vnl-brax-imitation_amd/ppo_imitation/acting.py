@@ -279,11 +279,12 @@ def _eval_fusable(env):
     return fz
 
 
-def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int) -> State:
+def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int, recorder=None) -> State:
     """`unroll_length` evaluation steps with no Transition log: per step the policy, ONE launch that steps, applies the
     Episode / AutoReset wrappers (its ops are the first-state restores only, every log pointer null) and scores
     (vnl_env_step_post_eval) and, with AutoResetWrapper(mode="fresh"), vnl_env_reset_done with no logs.  The device-noise
-    and reset counters advance once, after the loop, as in `_generate_unroll_fused`."""
+    and reset counters advance once, after the loop, as in `_generate_unroll_fused`.  `recorder` (a RolloutRecorder): one
+    more launch per step, vnl_env_record, after the step's launch and before the fresh reset."""
     import ctypes as C
 
     from .. import _lib
@@ -325,9 +326,9 @@ def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int) -
     dev_noise = _device_noise(policy)
     for t in range(T):
         if dev_noise:
-            actions, _ = policy(info["traj"], st.obs, None, step_offset=t, advance=False)
+            actions, pex = policy(info["traj"], st.obs, None, step_offset=t, advance=False)
         else:
-            actions, _ = policy(info["traj"], st.obs, key)
+            actions, pex = policy(info["traj"], st.obs, key)
         if epilogue:  # (the descriptors are copied into the launch's arguments by the call)
             base._post_desc, base._eval_desc = d, e
             try:
@@ -338,6 +339,8 @@ def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int) -
             base.step(st, actions)
             _lib.check(base._L, base._L.vnl_rollout_post(C.byref(d), B, stream))
             _lib.check(base._L, base._L.vnl_rollout_eval(C.byref(e), B, stream))
+        if recorder is not None:  # (first_state: the done row's state columns are the restored first state, as brax returns it)
+            recorder.record(st, actions, pex)
         if fresh:
             base.reset_done(st, st.done, seed=ar.seed, step_base=info["reset_step"], step_offset=t, env_offset=ar.env_offset)
     _evaluate_unroll_fused.hold = prev_done  # the launches are asynchronous
@@ -348,34 +351,50 @@ def _evaluate_unroll_fused(ew, fz, st: State, policy, key, unroll_length: int) -
     return st
 
 
-def evaluate_unroll(env, env_state: State, policy, key, unroll_length: int, fused: Optional[bool] = None) -> State:
+def evaluate_unroll(env, env_state: State, policy, key, unroll_length: int, fused: Optional[bool] = None,
+                    recorder=None) -> State:
     """`unroll_length` steps of EvalWrapper(...) `env` for their scores alone (info["eval_records"] and its companions): no
     Transition is kept.  `fused` (default: whenever possible) runs the wrappers and the scoring on the device,
-    `_evaluate_unroll_fused`; otherwise the wrappers step in torch ops.  The two give the same records, bit for bit."""
+    `_evaluate_unroll_fused`; otherwise the wrappers step in torch ops.  The two give the same records, bit for bit.
+    `recorder` (a RolloutRecorder): one row per step, written after the step's post-processing and scoring and before a fresh
+    auto-reset -- in "fresh" mode the done row holds the true terminal state, in "first_state" mode its state columns hold the
+    restored first state (what brax's wrapped env returns) beside the terminal step's reward, done, metrics and
+    termination_error.  Row 0, the reset state, is the caller's: `recorder.record(state)` after `env.reset`."""
     fz = _eval_fusable(env) if fused is not False else None
     if fused is True and fz is None:
         raise ValueError("fused evaluation needs EvalWrapper(AutoResetWrapper(EpisodeWrapper(<tracking env>))), action_repeat 1")
     if fz is not None:
-        st = _evaluate_unroll_fused(env, fz, env_state, policy, key, unroll_length)
+        st = _evaluate_unroll_fused(env, fz, env_state, policy, key, unroll_length, recorder)
         env.sync_eval_metrics(st)
         return st
+    # (under a fresh auto-reset the row must be written inside the step, between the scoring and the reset: EvalWrapper's hook)
+    hooked = recorder is not None and isinstance(env, EvalWrapper) and env._fresh() is not None
     for _ in range(unroll_length):
-        actions, _ = policy(env_state.info["traj"], env_state.obs, key)
-        env_state = env.step(env_state, actions)
+        actions, pex = policy(env_state.info["traj"], env_state.obs, key)
+        if hooked:
+            env.after_score = lambda st, a=actions, x=pex: recorder.record(st, a, x)
+        try:
+            env_state = env.step(env_state, actions)
+        finally:
+            if hooked:
+                env.after_score = None
+        if recorder is not None and not hooked:
+            recorder.record(env_state, actions, pex)
     return env_state
 
 
 class GraphedEval:
     """`evaluate_unroll` on the fused route with `graph_steps` steps captured ONCE into a hipGraph: an evaluation of
     `unroll_length` steps is `unroll_length // graph_steps` replays and an eager tail of the remaining steps.  Same kernels,
-    same arguments, same streams of noise as the eager fused route: the same records.
+    same arguments, same streams of noise as the eager fused route: the same records.  `recorder` (a RolloutRecorder): its
+    launch is captured with every step; the cursor lives on the device, so replays advance it.
 
     The graph works on the buffers of the `env_state` given here; `__call__(state)` copies another state of the same env
     (a new `env.reset`) into them first.  The policy's parameter tensors are fixed likewise (update them in place).  A
     generator policy needs `key` on the device (registered with the graph); a device-noise policy carries step offsets
     0..graph_steps-1 in the captured launches and the graph's last node advances its counter, as in GraphedUnroll."""
 
-    def __init__(self, env, env_state: State, policy, key, unroll_length: int, graph_steps: int = 20):
+    def __init__(self, env, env_state: State, policy, key, unroll_length: int, graph_steps: int = 20, recorder=None):
         fz = _eval_fusable(env)
         dev = env_state.obs.device
         if fz is None or dev.type != "cuda":
@@ -386,11 +405,12 @@ class GraphedEval:
         self.env, self.state, self.policy, self.key = env, env_state, policy, key
         self.graph_steps = max(1, min(int(graph_steps), int(unroll_length)))
         self.replays, self.tail = divmod(int(unroll_length), self.graph_steps)
-        self._fz = fz
-        args = (env, fz, env_state, policy, key, self.graph_steps)
+        self._fz, self.recorder = fz, recorder
+        args = (env, fz, env_state, policy, key, self.graph_steps, recorder)
         # warm-up on a side stream with everything put back afterwards, as in GraphedUnroll
         gen_state = policy.counter.clone() if dev_noise else key.get_state()
         saved = _snapshot_state(env_state)
+        saved_rec = recorder._snapshot() if recorder is not None else None
         base = fz[0].unwrapped
         saved_domain = (base._copy_domain_tables() if getattr(base, "domain_ranges", None) is not None or
                         getattr(base, "body_domain_ranges", None) is not None else None)
@@ -401,6 +421,8 @@ class GraphedEval:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         _restore_state(env_state, saved)
+        if saved_rec is not None:
+            recorder._restore(saved_rec)
         if saved_domain is not None:
             base._copy_domain_tables(saved_domain)
         self.graph = torch.cuda.CUDAGraph()
@@ -420,7 +442,7 @@ class GraphedEval:
         for _ in range(self.replays):
             self.graph.replay()
         if self.tail:
-            _evaluate_unroll_fused(self.env, self._fz, self.state, self.policy, self.key, self.tail)
+            _evaluate_unroll_fused(self.env, self._fz, self.state, self.policy, self.key, self.tail, self.recorder)
         self.env.sync_eval_metrics(self.state)
         return self.state
 
@@ -510,11 +532,14 @@ class Evaluator:
     device noise or `key` lives on the device) replays `graph_steps` captured steps at a time (GraphedEval).  Any other env
     goes through the generic `generate_unroll` loop.  `fused=False` forces that loop.
     `records` is the (N, 12) float32 array of the last evaluation's completed episodes (`_lib.EVAL_COLUMNS`, then the seven
-    metrics and the reward), envs in order, each env's episodes in order."""
+    metrics and the reward), envs in order, each env's episodes in order.
+    `record_envs` > 0: the first episode of the first `record_envs` envs is recorded step by step on the device
+    (RolloutRecorder: the reset row, then at most `record_steps` rows, default the unroll's length); `recorded` holds the last
+    evaluation's RecordedRollout.  With 0 nothing is allocated or launched."""
 
     def __init__(self, eval_env, eval_policy_fn, num_eval_envs: int, episode_length: int, action_repeat: int,
                  key: Optional[torch.Generator], episodes_per_env: int = 1, graphed: Optional[bool] = None,
-                 graph_steps: int = 20, fused: Optional[bool] = None):
+                 graph_steps: int = 20, fused: Optional[bool] = None, record_envs: int = 0, record_steps: Optional[int] = None):
         self._key = key
         self._eval_walltime = 0.0
         self._K = int(episodes_per_env)
@@ -528,11 +553,24 @@ class Evaluator:
         self._graphed, self._graph_steps, self._graph = graphed, int(graph_steps), None
         self.records: Optional[np.ndarray] = None
         self.state: Optional[State] = None  # the eval envs as the last evaluation left them
+        # recorded rollouts: the first episode of the first `record_envs` envs, one row per step after the reset row
+        self._recorder = None
+        if int(record_envs) > 0:
+            self._recorder = RolloutRecorder(self._env, num_record=int(record_envs),
+                                             capacity=1 + int(self._unroll if record_steps is None else record_steps))
+        self.recorded: Optional[RecordedRollout] = None  # the last evaluation's (None without record_envs)
 
     def _unroll_state(self, policy_params) -> State:
         """the state after the evaluation's unroll, by the route chosen at construction"""
         state = self._env.reset(self._key)
+        rec = self._recorder
+        if rec is not None:
+            rec.reset()
+            rec.record(state)
         if not self._fused:
+            if rec is not None:  # (the same steps as the loop below, the state alone kept)
+                return evaluate_unroll(self._env, state, self._policy_fn(policy_params), self._key, self._unroll, fused=False,
+                                       recorder=rec)
             state, _ = generate_unroll(self._env, state, self._policy_fn(policy_params), self._key, self._unroll)
             return state
         if self._graph is None:
@@ -542,11 +580,11 @@ class Evaluator:
             if self._graphed and not can:
                 raise ValueError("a graphed evaluation needs a HIP device and device noise or a generator on the device")
             if not (can if self._graphed is None else self._graphed):
-                return evaluate_unroll(self._env, state, policy, self._key, self._unroll, fused=True)
+                return evaluate_unroll(self._env, state, policy, self._key, self._unroll, fused=True, recorder=rec)
             # (the graph reads fixed parameter tensors: copies of its own, refreshed before every evaluation)
             self._params = tuple(_clone_param(p) for p in policy_params)
             self._graph = GraphedEval(self._env, state, self._policy_fn(self._params), self._key, self._unroll,
-                                      graph_steps=self._graph_steps)
+                                      graph_steps=self._graph_steps, recorder=rec)
         _copy_params(self._params, policy_params)
         return self._graph(state)
 
@@ -560,6 +598,8 @@ class Evaluator:
         count = state.info["eval_count"].cpu().numpy()
         recs = state.info["eval_records"].cpu().numpy()
         self.records = recs[np.arange(recs.shape[1])[None, :] < count[:, None]]
+        if self._recorder is not None:
+            self.recorded = self._recorder.result()
         metrics = {}
         if self._K == 1:
             per_episode = {name: v.cpu().numpy() for name, v in em.episode_metrics.items()}
@@ -579,3 +619,187 @@ class Evaluator:
         metrics["eval/sps"] = self._steps_per_unroll / epoch_eval_time
         self._eval_walltime += epoch_eval_time
         return {"eval/walltime": self._eval_walltime, **training_metrics, **metrics}
+
+
+# ---- recorded rollouts: per-step traces of chosen envs, written on the device (include/vnl.h vnl_record_desc) ----
+RECORD_COLUMNS = ("cur_frame", "clip_id", "steps", "done", "reward", "termination_error", "metrics", "qpos", "qvel", "action",
+                  "logits", "log_prob", "rand_log_prob")
+_RECORD_POLICY_COLUMNS = ("action", "logits", "log_prob", "rand_log_prob")
+# Private switch (tests compare the two): a row is written by vnl_env_record; False = by the restatement in torch ops,
+# which a library without the entry takes in any case.
+_RECORD_KERNEL = True
+
+
+@dataclasses.dataclass
+class RecordedRollout:
+    """What a RolloutRecorder has written, as NumPy arrays: `length` (R,) rows recorded per recorder, `env_index` (R,) the env
+    each watched, and per column an (R, capacity, w) array in `columns` (also reachable as attributes: `rec.qpos`), rows at or
+    beyond `length` zero.  `ref_qpos` (R, capacity, nq) is the reference clip's pose at the env's frame and
+    `render_qpos = concatenate([ref_qpos, qpos], -1)` what the reference hands its renderer (train.py:289-293).  Row 0 is the
+    reset state (its policy columns are NaN); row k pairs the policy outputs that chose action k with the state it led to."""
+
+    length: np.ndarray
+    env_index: np.ndarray
+    columns: Dict[str, np.ndarray]
+    ref_qpos: Optional[np.ndarray] = None
+
+    def __getattr__(self, name):
+        cols = self.__dict__.get("columns") or {}
+        if name in cols:
+            return cols[name]
+        raise AttributeError(name)
+
+    @property
+    def render_qpos(self) -> np.ndarray:
+        return np.concatenate([self.ref_qpos, self.columns["qpos"]], axis=-1)
+
+    def save(self, path) -> None:
+        extra = {} if self.ref_qpos is None else {"ref_qpos": self.ref_qpos}
+        np.savez(path, length=self.length, env_index=self.env_index, **extra, **{"col." + k: v for k, v in self.columns.items()})
+
+    @classmethod
+    def load(cls, path) -> "RecordedRollout":
+        with np.load(path) as z:
+            return cls(length=z["length"], env_index=z["env_index"], ref_qpos=z["ref_qpos"] if "ref_qpos" in z else None,
+                       columns={k[4:]: z[k] for k in z.files if k.startswith("col.")})
+
+
+class RolloutRecorder:
+    """One row per `record(state, action, policy_extras)` call for each of R recorders, in ONE launch (vnl_env_record): the
+    reference pose of the env's clip at its frame, then the columns RECORD_COLUMNS read from `state` and the policy's outputs,
+    then `extra` -- {name: (B[, w]) float32 / int32 tensor on the env's device}, read live at every call (a decoder policy's
+    `latent_out`, say); at most 16 columns in all.  Recorder r watches env `env_index[r]` (default: env r of the first
+    `num_record`); an index outside the batch records nothing.  `capacity` rows per recorder; with `stop_at_done` a recorder
+    closes after the row on which its env's `done` is set.  `rows`, `count` and `open` live on the device and the call has no
+    host synchronisation: it can be captured in a hipGraph, whose replays advance the cursor.  A column the state or the call
+    does not have (no `steps` without an EpisodeWrapper; no policy outputs and no `extra` on the reset row, the call without
+    an action) is NaN words."""
+
+    def __init__(self, env, num_record: Optional[int] = None, env_index=None, capacity: int = 1, stop_at_done: bool = True,
+                 extra: Optional[Dict[str, torch.Tensor]] = None):
+        base = env.unwrapped
+        self.base, self.device, B = base, base.device, base.num_envs
+        if (num_record is None) == (env_index is None):
+            raise ValueError("give num_record or env_index")
+        if env_index is not None:
+            self.env_index = torch.as_tensor(env_index, dtype=torch.int32).reshape(-1).to(self.device).contiguous()
+            R = int(self.env_index.numel())
+        else:
+            self.env_index, R = None, int(num_record)
+        if R < 1 or int(capacity) < 1:
+            raise ValueError("a recorder needs at least one env and a capacity of at least 1")
+        d = base.dims
+        nq, nv, nu = int(d.nq), int(d.nv), int(d.nu)
+        widths = dict(cur_frame=1, clip_id=1, steps=1, done=1, reward=1, termination_error=1, metrics=7, qpos=nq, qvel=nv,
+                      action=nu, logits=2 * nu, log_prob=1, rand_log_prob=1)
+        self.extra = dict(extra or {})
+        for k, t in self.extra.items():
+            if k in widths or t.dtype not in (torch.float32, torch.int32) or t.dim() not in (1, 2) or t.shape[0] != B or \
+                    not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"extra[{k!r}] must be a new name and a contiguous float32 / int32 ({B}[, w]) tensor on the env's device")
+        self.columns = [(k, widths[k]) for k in RECORD_COLUMNS] + [(k, t.numel() // B) for k, t in self.extra.items()]
+        from .. import _lib
+
+        if len(self.columns) > _lib.RECORD_MAX_COLS:
+            raise ValueError(f"at most {_lib.RECORD_MAX_COLS} columns: {_lib.RECORD_MAX_COLS - len(RECORD_COLUMNS)} extra ones")
+        self._int = {"cur_frame", "clip_id"} | {k for k, t in self.extra.items() if t.dtype == torch.int32}
+        self.nq, self.num_record, self.capacity, self.stop_at_done = nq, R, int(capacity), bool(stop_at_done)
+        self.row_width = nq + sum(w for _, w in self.columns)
+        self.rows = torch.zeros((R, self.capacity, self.row_width), dtype=torch.float32, device=self.device)
+        self.count = torch.zeros(R, dtype=torch.int32, device=self.device)
+        self.open = torch.ones(R, dtype=torch.int32, device=self.device)
+        self._ref = None  # (C, T, nq) int32 words of the clip's pose, for the restatement
+        self._hold = None
+
+    def reset(self) -> None:
+        """rearm: every recorder open at row 0 (the rows are zeroed)"""
+        self.rows.zero_()
+        self.count.zero_()
+        self.open.fill_(1)
+
+    def _sources(self, state: State, action, policy_extras):
+        raw, info, ps = state.info["_raw"], state.info, state.pipeline_state
+        px = dict(policy_extras or {})
+        src = dict(cur_frame=raw["cur_frame"], clip_id=raw["clip_id"], steps=info.get("steps"), done=state.done,
+                   reward=state.reward, termination_error=raw["termination_error"], metrics=raw["metrics"], qpos=ps.raw("qpos"),
+                   qvel=ps.raw("qvel"), action=action, logits=px.get("logits"), log_prob=px.get("log_prob"),
+                   rand_log_prob=px.get("rand_log_prob"),
+                   **{k: (t if action is not None else None) for k, t in self.extra.items()})  # (no action: the reset row)
+        B, out = self.base.num_envs, []
+        for k, w in self.columns:
+            t = src[k]
+            if t is not None:
+                want = torch.int32 if k in self._int else torch.float32
+                if t.dtype != want or t.device != self.device or t.shape[0] != B or t.numel() != B * w:
+                    raise ValueError(f"column {k!r} must be a {want} ({B}, {w}) tensor on the env's device, got {t.dtype} "
+                                     f"{tuple(t.shape)}")
+                t = t.contiguous()
+            out.append(t)
+        return out, raw
+
+    def record(self, state: State, action: Optional[torch.Tensor] = None, policy_extras: Optional[dict] = None) -> None:
+        """one row for every open recorder: the state as it stands, beside the action that led to it and the policy outputs
+        that chose the action (none: the reset row)"""
+        from .. import _lib
+
+        srcs, raw = self._sources(state, action, policy_extras)
+        L = self.base._L
+        if not (_RECORD_KERNEL and hasattr(L, "vnl_env_record")):
+            return self._record_torch(srcs, raw, state.done)
+        import ctypes as C
+
+        d = _lib.RecordDesc()
+        d.env_index = self.env_index.data_ptr() if self.env_index is not None else None
+        d.done, d.ref_frame, d.ref_clip = state.done.data_ptr(), raw["cur_frame"].data_ptr(), raw["clip_id"].data_ptr()
+        d.count, d.open, d.rows = self.count.data_ptr(), self.open.data_ptr(), self.rows.data_ptr()
+        d.num_rec, d.capacity, d.row_width = self.num_record, self.capacity, self.row_width
+        d.stop_at_done, d.num_cols = int(self.stop_at_done), len(self.columns)
+        for o, t, (_, w) in zip(d.cols, srcs, self.columns):
+            o.src, o.width = (t.data_ptr() if t is not None else None), w
+        _lib.check(L, L.vnl_env_record(self.base._env_h, C.byref(d), self.base._stream()))
+        self._hold = srcs  # the launch is asynchronous: keep this step's sources alive
+
+    def _record_torch(self, srcs, raw, done) -> None:
+        """include/vnl.h above vnl_record_desc in torch ops: the same words in rows, count and open"""
+        base, dev, R, B = self.base, self.device, self.num_record, self.base.num_envs
+        if self._ref is None:
+            c = base._clip
+            pose = np.concatenate([c["position"], c["quaternion"], c["joints"]], axis=-1).astype(np.float32)
+            self._ref = torch.from_numpy(np.ascontiguousarray(pose)).to(dev).view(torch.int32)
+        idx = (self.env_index if self.env_index is not None else torch.arange(R, dtype=torch.int32, device=dev)).long()
+        valid = (idx >= 0) & (idx < B) & (self.open != 0) & (self.count < self.capacity)
+        e = idx.clamp(0, B - 1)
+        Cn, Tn = self._ref.shape[:2]
+        frame, clip = raw["cur_frame"][e].long().clamp(0, Tn - 1), raw["clip_id"][e].long().clamp(0, Cn - 1)
+        parts = [self._ref[clip, frame]]
+        for t, (_, w) in zip(srcs, self.columns):
+            parts.append(t.view(torch.int32).reshape(B, w)[e] if t is not None else
+                         torch.full((R, w), 0x7FC00000, dtype=torch.int32, device=dev))
+        row = torch.cat(parts, dim=1)
+        words = self.rows.view(torch.int32)
+        r, slot = torch.arange(R, device=dev), self.count.clamp(max=self.capacity - 1).long()
+        words[r, slot] = torch.where(valid[:, None], row, words[r, slot])
+        self.count += valid.to(torch.int32)
+        if self.stop_at_done:
+            self.open.copy_(torch.where(valid & (done[e] != 0), torch.zeros_like(self.open), self.open))
+
+    def result(self) -> RecordedRollout:
+        """the rows recorded so far (synchronises with the device)"""
+        rows = self.rows.cpu().numpy()  # (rows at or beyond the count are zero: zeroed by `reset`, never written since)
+        length = self.count.cpu().numpy().copy()
+        at, cols = self.nq, {}
+        ref = np.ascontiguousarray(rows[:, :, :at])
+        for k, w in self.columns:
+            a = np.ascontiguousarray(rows[:, :, at:at + w])
+            cols[k] = a.view(np.int32) if k in self._int else a
+            at += w
+        idx = self.env_index.cpu().numpy().copy() if self.env_index is not None else np.arange(self.num_record, dtype=np.int32)
+        return RecordedRollout(length=length, env_index=idx, columns=cols, ref_qpos=ref)
+
+    # (a graph capture's warm-up runs real steps: what it wrote is put back)
+    def _snapshot(self):
+        return self.rows.clone(), self.count.clone(), self.open.clone()
+
+    def _restore(self, saved) -> None:
+        for t, s in zip((self.rows, self.count, self.open), saved):
+            t.copy_(s)

@@ -154,6 +154,8 @@ def train(
     body_inertia_with_mass: bool = False,
     eval_episodes_per_env: int = 1,
     eval_auto_reset: str = "first_state",
+    eval_record_envs: int = 0,
+    eval_record_steps: Optional[int] = None,
 ):
     """PPO training (train.py:62-491).
 
@@ -215,6 +217,11 @@ def train(
     ones -- start frame, clip and reset noise drawn on the device on the eval seed -- and `domain_ranges` /
     `body_domain_ranges` go to its wrapper, so that every eval episode has a domain of its own; start priorities stay off
     for the evaluator.  The defaults are the reference's evaluation: K = 1 from the cached first state.
+
+    `eval_record_envs` (and `eval_record_steps`): every evaluation records the first episode of that many eval envs step by
+    step on the device (acting.Evaluator record_envs / record_steps, acting.RolloutRecorder) -- what the reference's
+    policy_params_fn collects with a Python loop (train.py:154-331); `train.last_evaluator.recorded` is the last evaluation's
+    RecordedRollout, for a `policy_params_fn` to read.  With 0 nothing is allocated or launched.
 
         `capture_graph` (default: on for HIP devices): the minibatch step (gather -> loss -> backward
     [-> Adam when single-GPU]) is captured once into a hipGraph and replayed -- the eager step is
@@ -657,7 +664,9 @@ def train(
                                            reset_info_on_autoreset=reset_info_on_autoreset)
         evaluator = acting.Evaluator(ev_wrapped, functools.partial(make_policy, deterministic=deterministic_eval, **eval_kw),
                                      num_eval_envs=num_eval_envs, episode_length=episode_length,
-                                     action_repeat=action_repeat, key=g_eval, episodes_per_env=eval_episodes_per_env)
+                                     action_repeat=action_repeat, key=g_eval, episodes_per_env=eval_episodes_per_env,
+                                     record_envs=eval_record_envs, record_steps=eval_record_steps)
+        train.last_evaluator = evaluator  # (already here: a policy_params_fn reads its `recorded` during the run)
 
     def inference_params():
         return (training_state.normalizer_params.clone(), training_state.params.detach()[:n_pol].clone())
