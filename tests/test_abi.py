@@ -84,3 +84,42 @@ def test_argument_validation_of_the_helper_entry_points():
     assert lib.vnl_ppo_head(C.byref(a), work, None) == -1 and b"null buffer" in lib.vnl_last_error()
     assert lib.vnl_policy_forward(None, None, None, None, None, None, None, None, 1, 0, None, None, None, None, None,
                                   None, None, None, None) == -1
+
+
+def test_argument_validation_of_gather_and_adam():
+    """vnl_gather_rows / vnl_adam_step reject malformed arguments with VNL_ERR_ARG and a message, and launch nothing: on the
+    host build a launch would run at once, read the pointers below (never dereferenceable) and write the buffers watched."""
+    lib = H.hostsim_library("float")
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    src, idx = torch.arange(12, dtype=torch.float32).reshape(1, 4, 3), torch.tensor([2, 0], dtype=torch.int64)
+    dst = torch.full((1, 2, 3), -7.0)
+
+    def desc(**over):
+        d = _lib.GatherDesc()
+        d.idx, d.N, d.M, d.num_ops = ptr(idx), 4, 2, 1
+        d.ops[0].dst, d.ops[0].src, d.ops[0].T, d.ops[0].width = ptr(dst), ptr(src), 1, 3
+        for k, v in over.items():
+            setattr(d.ops[0] if k in ("dst", "src", "T", "width") else d, k, v)
+        return d
+
+    def rejected(d, message):
+        rc = lib.vnl_gather_rows(C.byref(d) if d is not None else None, None)
+        return rc == -1 and message in lib.vnl_last_error() and bool((dst == -7.0).all())
+
+    assert rejected(None, b"bad descriptor")
+    for over in (dict(idx=None), dict(N=0), dict(N=-1), dict(M=0), dict(M=-3), dict(num_ops=_lib.POST_MAX_OPS + 1)):
+        assert rejected(desc(**over), b"bad descriptor"), over
+    for over in (dict(dst=None), dict(src=None), dict(T=0), dict(T=-1), dict(width=0), dict(width=-2)):
+        assert rejected(desc(**over), b"bad op"), over
+    assert lib.vnl_gather_rows(C.byref(desc()), None) == 0 and torch.equal(dst, src[:, idx])  # (the descriptor they all vary)
+
+    p, g, mu, nu = (torch.full((3,), v) for v in (1.0, 0.5, 0.25, 0.125))
+    count = torch.tensor([1], dtype=torch.int64)
+    good = [ptr(p), ptr(g), ptr(mu), ptr(nu), ptr(count)]
+    for k in range(5):
+        args = list(good)
+        args[k] = None
+        assert lib.vnl_adam_step(*args, 3, 1e-3, 0.9, 0.999, 1e-8, None) == -1 and b"vnl_adam_step" in lib.vnl_last_error(), k
+    for n in (0, -5):
+        assert lib.vnl_adam_step(*good, n, 1e-3, 0.9, 0.999, 1e-8, None) == -1 and b"vnl_adam_step" in lib.vnl_last_error(), n
+    assert all(bool((t == v).all()) for t, v in ((p, 1.0), (g, 0.5), (mu, 0.25), (nu, 0.125))) and int(count) == 1

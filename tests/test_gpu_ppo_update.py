@@ -101,11 +101,18 @@ def test_hip_update_matches_autograd_and_numpy(cfg):
         assert np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-12) < 1e-5, name
     got = upd.buffer("values").cpu().numpy().astype(np.float64)[: T * B].reshape(T, B)
     assert np.abs(got - values).max() / max(np.abs(values).max(), 1e-12) < 1e-5
+    # the advantages buffer (before normalisation) against intention_losses.compute_gae in float64
+    t64 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))  # noqa: E731
+    trunc = t64(npd(data.extras["state_extras"]["truncation"]))
+    bootstrap = PN.value_forward(views_v, len(cfg["val"]) + 1, (npd(data.next_observation[-1]) - npd(norm.mean)) / npd(norm.std))
+    _, adv_ref = intention_losses.compute_gae(
+        truncation=trunc, termination=(1 - t64(npd(data.discount))) * (1 - trunc), rewards=t64(npd(data.reward)) * HP["reward_scaling"],
+        values=t64(values), bootstrap_value=t64(bootstrap), lambda_=HP["gae_lambda"], discount=HP["discounting"])
+    adv_ref = adv_ref.numpy()
     for name in ("vs", "advantages"):
         got = upd.buffer(name).cpu().numpy().astype(np.float64).reshape(T, B)
-        ref = parts[name] if name == "vs" else None
-        if ref is not None:
-            assert np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-12) < 1e-5, name
+        ref = parts[name] if name == "vs" else adv_ref
+        assert np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-12) < 1e-5, name
 
 
 def test_forward_routes_of_the_intention_network_agree():
